@@ -3,10 +3,14 @@
 (forward + multibox loss + backward + Keras-SGD update, data-parallel gradient all-reduce when N > 1).
 
     python bench.py --gpus N --steps K --warmup W [--archi deconv|ssd_custom|up_sampling] [--batch 32]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`,
 one rank per GPU over RCCL.  Inputs (synthetic JPEG-DCT coefficients + encoder-made targets) are resident
-in HBM before the timed region.  Rank 0 prints ONE JSON line.
+in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times K steps and
+reports them; `--full` adds the `roofline` object, the `secondary` list and the `cpu_baseline` sample, each of which
+runs work of its own.  The last timed step starts from the seeded initial state (run_workload), and
+`--dump-outputs DIR` writes what it computed (dump_outputs()).
 """
 import argparse
 import json
@@ -211,18 +215,37 @@ def run_workload(archi, floatx, batch, steps, warmup, rank=0, world=1):
             if torch.distributed.is_initialized():
                 torch.distributed.barrier()
 
+        # what a step carries into the next one: weights + BatchNormalization statistics (the 16-bit weight shadows are
+        # made from them at the start of every forward), SGD velocity, the optimizer's iteration count
+        st, opt = model._store, model.optimizer
+        start = (st["flat"].clone(), st["vel"].clone(), opt.iterations)
+
+        def timed(n):
+            t0 = time.perf_counter()
+            for _ in range(n):
+                model.run_train_step(plan)
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
         for _ in range(warmup):
             model.run_train_step(plan)
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            model.run_train_step(plan)
+        elapsed = timed(steps - 1)
+        # The last timed step starts again from the seeded state the warm-up started from, so that what it computes
+        # (loss, y_pred, updated weights: --dump-outputs) is the same in every run up to rounding.  A chain of steps is
+        # not: the backward GEMMs sum with fp32 atomics, and every step amplifies those last-bit differences ~1000x
+        # through the weights it hands on (y_pred rel-L2 ~8e-6 after 2 steps, ~0.1 after 5).  The reset is untimed.
+        st["flat"].copy_(start[0])
+        st["vel"].copy_(start[1])
+        opt.iterations = start[2]
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
-        elapsed = time.perf_counter() - t0
+        elapsed += timed(1)
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -318,6 +341,31 @@ def roofline_of(archi, floatx, batch, value, world, model, plan):
     return roof
 
 
+# elements per dumped array (float32): 40 MiB + 16 MiB + the loss, inside the 64 MB bound of a dump
+DUMP_MAX_ELEMENTS = {"y_pred": 10 << 20, "weights": 4 << 20}
+
+
+def dump_outputs(out_dir, model, plan, loss):
+    """What the last timed step handed its caller, as .npy files in `out_dir`, so that two builds can be compared output
+    for output on the same seeded inputs: `loss` (float64, the value train_on_batch returns), `y_pred` (float32, that
+    step's predictions) and `weights` (float32, the flat parameter and BatchNormalization state after its SGD update).
+    An array with more elements than DUMP_MAX_ELEMENTS allows is replaced by a fixed sample of its flattened elements
+    (torch.randperm seeded with 1234, in index order).
+    The last timed step starts from the seeded initial state (run_workload), so with the same arguments y_pred and the loss
+    are the same in every run and the weights differ by the rounding of the backward's fp32-atomic sums (rel-L2 ~1e-8)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    for name, t in (("y_pred", plan.outputs[0].buf), ("weights", model.flat_all)):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMENTS[name]:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(1234))[:DUMP_MAX_ELEMENTS[name]]
+            arr = flat[idx.sort().values.to(flat.device)].float().cpu().numpy()
+        else:
+            arr = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 # the non-headline single-GPU configurations of BASELINE.json, measured by the same run so that the driver's record holds
 # them too (VERDICT r2 item 3): config 3 and the two workloads of config 5 -- and the headline workload with fp32 MFMA
 # instructions only (what `value` measured in rounds 1-2) and in the float32x3 arithmetic (fp32 tensors, ~4e-6 per GEMM:
@@ -339,11 +387,18 @@ def main(json_out=None):
                          "headline); float32_mfma = fp32 MFMA instructions only; float32x6 / float32x3 = the split kernels "
                          "everywhere; float16 / bfloat16 = BASELINE config 5's reduced-precision MFMA with fp32 master weights "
                          "and accumulation (each reported with its own dtype)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` list (config 3 / config 5 workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the `roofline` object (one extra step, every conv "
+                         "launch timed), the `secondary` list and the `cpu_baseline` sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` sample")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the `secondary` list (config 3 / config 5 workloads)")
     ap.add_argument("--cpu-batch", type=int, default=8, help="batch of the CPU-oracle sample (BASELINE.md: 8)")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of CPU work for the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from jpeg_detection_resnet_ssd_amd import dist as djdist
     from jpeg_detection_resnet_ssd_amd import workloads
@@ -363,6 +418,8 @@ def main(json_out=None):
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, plan, loss)
     images = world * args.batch * args.steps
     value = images / elapsed
     gflop = workloads.TRAIN_GFLOP_PER_IMAGE[args.archi]
@@ -383,6 +440,9 @@ def main(json_out=None):
                                 "1 GPU; the RCCL exchange has only ever run on a 1-rank communicator (no multi-GPU box "
                                 "was available to the builder): no scaling curve has been measured"},
     }
+    if not args.full:     # a plain run reports the headline alone; what takes runs of its own is behind --full
+        print(json.dumps(out), file=json_out or sys.stdout, flush=True)
+        return
     out["roofline"] = roofline_of(args.archi, args.floatx, args.batch, value, world, model, plan)
     del model, plan
     torch.cuda.empty_cache()

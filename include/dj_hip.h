@@ -400,6 +400,20 @@ int dj_ssd_encode_targets(const double* labels, const int* n_gt, int batch, int 
 int dj_global_avg_pool_fwd(const float* x, float* y, int B, int HW, int C, void* stream);
 int dj_global_avg_pool_bwd(const float* dy, float* dx, int B, int HW, int C, int beta, void* stream);
 
+/* ---- RGB batch -> de-quantised JPEG DCT coefficient tensors, what `Image.fromarray(x).save(f, format="jpeg")` followed by
+ * `jpeg2dct.numpy.loads` yields (L/data_generator/object_detection_2d_data_generator_dct_j2d.py:1167-1195), bit for bit and
+ * without the file in between: libjpeg's integer RGB->YCbCr, 4:2:0 box downsampling, "slow" integer forward DCT and
+ * quantisation, then the multiplication by the table again (normalized != 0) or the bare level (normalized == 0).
+ * rgb: DEVICE [batch][height][width][3] bytes, `stride_bytes` between pixel rows, images dense (height * stride_bytes apart).
+ * luma_table / chroma_table: HOST pointers to 64 entries in natural (row-major) order, each 1..255; they travel as kernel
+ * arguments, so the call stays capturable.  Outputs are float32 NHWC block tensors, channel 8*u+v = vertical frequency u,
+ * horizontal frequency v: out_y [batch][ceil(h/8)][ceil(w/8)] pixels of ld_y floats, out_cb / out_cr
+ * [batch][ceil(ceil(h/2)/8)][ceil(ceil(w/2)/8)] pixels of ld_cb / ld_cr floats (each >= 64: Cb and Cr may be the two
+ * channel halves of one 128-channel tensor).  Only the 64 channels of each pixel are written. ---- */
+int dj_rgb_to_dct(const unsigned char* rgb, int batch, int height, int width, long stride_bytes,
+                  const unsigned short* luma_table, const unsigned short* chroma_table, int normalized, float* out_y,
+                  long ld_y, float* out_cb, long ld_cb, float* out_cr, long ld_cr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

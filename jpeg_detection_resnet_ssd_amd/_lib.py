@@ -146,6 +146,8 @@ SIGNATURES = {
                                       c_int, c_double, c_double, c_int, FP, c_void_p]),
     "dj_global_avg_pool_fwd": (c_int, [FP, FP, c_int, c_int, c_int, c_void_p]),
     "dj_global_avg_pool_bwd": (c_int, [FP, FP, c_int, c_int, c_int, c_int, c_void_p]),
+    "dj_rgb_to_dct": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_int, FP, c_long, FP, c_long, FP,
+                              c_long, c_void_p]),
 }
 
 

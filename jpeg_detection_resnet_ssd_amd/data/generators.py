@@ -30,7 +30,10 @@ class SyntheticDataGeneratorDCT(object):
 
     def generate(self, batch_size=32, shuffle=True, transformations=(), label_encoder=None,
                  returns=("processed_images", "encoded_labels"), keep_images_without_gt=False, deconv=False,
-                 fast=True, **kwargs):
+                 fast=True, dct_emitter=None, **kwargs):
+        """`dct_emitter` (data/jpeg_dct.py:DeviceDCTEmitter): the batch is `synthetic_dct.smooth_random_image` PIXELS
+        handed to the emitter -- the JPEG transform then runs on the GPU when the model uploads the batch -- instead of
+        coefficients computed here."""
         if "image_ids" in returns or "inverse_transform" in returns or "processed_labels" in returns:
             for item in self._generate_indexed(batch_size, label_encoder, returns, deconv):
                 yield item
@@ -39,8 +42,12 @@ class SyntheticDataGeneratorDCT(object):
         pool = max(1, self.n_images // batch_size)
         while True:
             s = self.seed + (step % pool)
-            x = (sd.fast_dct_batch(batch_size, seed=s, split_chroma=deconv) if fast
-                 else sd.dct_batch(batch_size, seed=s, split_chroma=deconv))
+            if dct_emitter is not None:
+                rng = np.random.default_rng(s)
+                x = dct_emitter(np.stack([sd.smooth_random_image(rng) for _ in range(batch_size)]))
+            else:
+                x = (sd.fast_dct_batch(batch_size, seed=s, split_chroma=deconv) if fast
+                     else sd.dct_batch(batch_size, seed=s, split_chroma=deconv))
             gt = sd.random_ground_truth(batch_size, seed=s)
             y = label_encoder(gt) if label_encoder is not None else gt
             step += 1
@@ -69,3 +76,11 @@ class SyntheticDataGeneratorDCT(object):
             if "inverse_transform" in returns:
                 ret.append([[] for _ in idx])
             yield ret
+
+
+def with_device_dct(generator, emitter):
+    """Adapter for a generator that yields `(uint8 RGB batch (B, H, W, 3), labels, ...)`: the pixels are wrapped by
+    `emitter` (data/jpeg_dct.py:DeviceDCTEmitter) so that `Model.fit_generator` turns them into the DCT inputs on the
+    GPU; everything after the first item passes through."""
+    for item in generator:
+        yield (emitter(item[0]),) + tuple(item[1:])

@@ -406,9 +406,24 @@ class Model(object):
         return list(x) if isinstance(x, (list, tuple)) else [x]
 
     def _upload(self, plan, x, y):
-        xs = self._as_list(x)
-        if len(xs) != len(plan.inputs):
-            raise ValueError("Error when checking model input: expected %d arrays but got %d" % (len(plan.inputs), len(xs)))
+        if isinstance(x, (list, tuple)) and len(x) == 1 and hasattr(x[0], "emit_into"):
+            x = x[0]                     # (`predict` slices its inputs into a list)
+        if hasattr(x, "emit_into"):      # PendingDCTInputs: the pixels go up, the JPEG transform runs on the device
+            shapes = [tuple(s) for s in x.shapes]
+            if len(shapes) != len(plan.inputs):
+                raise ValueError("Error when checking model input: expected %d arrays but got %d"
+                                 % (len(plan.inputs), len(shapes)))
+            for buf, shp in zip(plan.inputs, shapes):
+                if shp != tuple(buf.shape):
+                    raise ValueError("Error when checking input: expected shape %s but got array with shape %s"
+                                     % (tuple(buf.shape), shp))
+            x.emit_into(plan.inputs)
+            xs = []
+        else:
+            xs = self._as_list(x)
+            if len(xs) != len(plan.inputs):
+                raise ValueError("Error when checking model input: expected %d arrays but got %d"
+                                 % (len(plan.inputs), len(xs)))
         for buf, arr in zip(plan.inputs, xs):
             t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
             if tuple(t.shape) != tuple(buf.shape):

@@ -322,3 +322,38 @@ def bn_bwd_apply_call(dy, ld_dy, z, ld_z, mask_y, ld_y, scale, shift, mode, k0, 
                 int(dm_beta))
     return ("dj_bn_bwd_apply", dy, int(ld_dy), z, int(ld_z), mask_y, int(ld_y), scale, shift, int(mode), k0, k1, k2, dz,
             int(ld_dz), int(rows), int(c), dm, int(ld_dm), int(dm_beta))
+
+
+# ---- RGB batch -> JPEG DCT coefficient tensors ------------------------------------------------------------------------------
+def _table_u16(table, what):
+    import ctypes
+    import numpy as np
+    t = np.ascontiguousarray(np.asarray(table).reshape(-1))
+    if t.size != 64 or (t != np.floor(t)).any() or t.min() < 0 or t.max() > 65535:
+        raise ValueError("%s quantisation table: expected 64 integer entries in natural order" % what)
+    return (ctypes.c_ushort * 64)(*[int(v) for v in t])
+
+
+def rgb_to_dct(rgb_u8, tables, outs, normalized=True, stream=None):
+    """(B, H, W, 3) uint8 CUDA tensor -> the de-quantised DCT coefficients of its baseline 4:2:0 JPEG, written into
+    `outs` = (y, cb, cr): float32 NHWC block tensors (B, ceil(H/8), ceil(W/8), 64) and twice (B, ceil(ceil(H/2)/8),
+    ceil(ceil(W/2)/8), 64), each of which may be a 64-channel slice of a wider buffer.  `tables` = (luma, chroma), 64
+    entries each in natural order (data/jpeg_dct.py:quant_tables).  `stream`: a HIP stream handle (None: the current
+    launch stream)."""
+    assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3, \
+        "expected a (B, H, W, 3) uint8 CUDA tensor"
+    b, h, w, _ = rgb_u8.shape
+    assert rgb_u8.stride(3) == 1 and rgb_u8.stride(2) == 3, "pixels must be packed RGB"
+    stride = rgb_u8.stride(1) if h > 1 else 3 * w
+    assert b == 1 or rgb_u8.stride(0) == h * stride, "images must be dense"
+    y, cb, cr = outs
+    yg = (-(-h // 8), -(-w // 8))
+    cg = (-(-(-(-h // 2)) // 8), -(-(-(-w // 2)) // 8))
+    for t, g, name in ((y, yg, "y"), (cb, cg, "cb"), (cr, cg, "cr")):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (b,) + g + (64,), \
+            "%s: expected float32 %s, got %s %s" % (name, (b,) + g + (64,), t.dtype, tuple(t.shape))
+    luma, chroma = tables
+    check(_L().dj_rgb_to_dct(ptr(rgb_u8), b, h, w, stride, _table_u16(luma, "luma"), _table_u16(chroma, "chroma"),
+                             int(bool(normalized)), ptr(y), _pixel_ld(y), ptr(cb), _pixel_ld(cb), ptr(cr), _pixel_ld(cr),
+                             stream if stream is not None else _stream()), "dj_rgb_to_dct")
+    return outs

@@ -24,6 +24,101 @@ struct VecIO<1> {
 };
 
 // ---------------------------------------------------------------------------------
+// Tensors that carry their storage type (float16 mode: activations held as fp16 and their gradients as bf16 in HBM inside
+// the backbone, fp32 elsewhere).  Five passes -- BN apply / Add+ReLU, the BN backward sums, BN backward apply, ReLU
+// backward and the strided copy -- each have ONE body, written against dj_ldt / dj_stt and compiled twice:
+//   TYPED = false  the type codes are never looked at and every access is a plain fp32 one: what the float entry points
+//                  (dj_affine_act, ...) launch, the code of the exact-fp32 mode;
+//   TYPED = true   every tensor operand comes with a type code (DJ_F32 / DJ_F16 / DJ_BF16), looked at per access with a
+//                  wave-uniform branch -- these passes are HBM-bound, the branch is free: what the `_t` entry points
+//                  launch, whatever the codes are.
+// All arithmetic stays fp32.  A 4-element piece of a 16-bit tensor is one 8-byte access.
+// ---------------------------------------------------------------------------------
+typedef unsigned int dj_u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 dj_h4 __attribute__((ext_vector_type(4)));
+
+template <int VEC, bool TYPED>
+__device__ __forceinline__ f32x4 dj_ldt(const void* base, long idx, int dt) {
+  if (!TYPED || dt == DJ_F32) return VecIO<VEC>::ld(reinterpret_cast<const float*>(base) + idx);
+  if (VEC == 4) {
+    const dj_u32x2 v = *reinterpret_cast<const dj_u32x2*>(reinterpret_cast<const unsigned short*>(base) + idx);
+    if (dt == DJ_F16) {
+      const dj_h4 h = __builtin_bit_cast(dj_h4, v);
+      return f32x4{(float)h.x, (float)h.y, (float)h.z, (float)h.w};
+    }
+    return f32x4{__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xFFFF0000u),
+                 __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xFFFF0000u)};
+  }
+  const unsigned short u = reinterpret_cast<const unsigned short*>(base)[idx];
+  const float f = (dt == DJ_F16) ? (float)__builtin_bit_cast(_Float16, u) : __builtin_bit_cast(float, (unsigned)u << 16);
+  return f32x4{f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ unsigned dj_pack2(float lo, float hi, int dt) {
+  if (dt == DJ_F16) {
+    const _Float16 a = (_Float16)lo, b = (_Float16)hi;
+    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+  }
+  const __bf16 a = (__bf16)lo, b = (__bf16)hi;   // round to nearest even
+  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+}
+
+template <int VEC, bool TYPED>
+__device__ __forceinline__ void dj_stt(void* base, long idx, int dt, f32x4 v) {
+  if (!TYPED || dt == DJ_F32) {
+    VecIO<VEC>::st(reinterpret_cast<float*>(base) + idx, v);
+  } else if (VEC == 4) {
+    *reinterpret_cast<dj_u32x2*>(reinterpret_cast<unsigned short*>(base) + idx) = dj_u32x2{dj_pack2(v.x, v.y, dt), dj_pack2(v.z, v.w, dt)};
+  } else {
+    reinterpret_cast<unsigned short*>(base)[idx] = (unsigned short)(dj_pack2(v.x, 0.f, dt) & 0xFFFFu);
+  }
+}
+
+// eight consecutive elements: ONE 16-byte access of a 16-bit tensor (two of a fp32 one) -- twice the bytes in flight per
+// thread of the 4-element form, which is what these HBM-bound passes are short of when every tensor is 16 bits wide
+typedef unsigned int dj_u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 dj_h8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void dj_ld8(const void* base, long idx, int dt, f32x4& lo, f32x4& hi) {
+  if (dt == DJ_F32) {
+    lo = VecIO<4>::ld(reinterpret_cast<const float*>(base) + idx);
+    hi = VecIO<4>::ld(reinterpret_cast<const float*>(base) + idx + 4);
+    return;
+  }
+  const dj_u32x4 v = *reinterpret_cast<const dj_u32x4*>(reinterpret_cast<const unsigned short*>(base) + idx);
+  if (dt == DJ_F16) {
+    const dj_h8 h = __builtin_bit_cast(dj_h8, v);
+    lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+  } else {
+    lo = f32x4{__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xFFFF0000u),
+               __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xFFFF0000u)};
+    hi = f32x4{__builtin_bit_cast(float, v.z << 16), __builtin_bit_cast(float, v.z & 0xFFFF0000u),
+               __builtin_bit_cast(float, v.w << 16), __builtin_bit_cast(float, v.w & 0xFFFF0000u)};
+  }
+}
+__device__ __forceinline__ void dj_st8(void* base, long idx, int dt, f32x4 lo, f32x4 hi) {
+  if (dt == DJ_F32) {
+    VecIO<4>::st(reinterpret_cast<float*>(base) + idx, lo);
+    VecIO<4>::st(reinterpret_cast<float*>(base) + idx + 4, hi);
+  } else {
+    *reinterpret_cast<dj_u32x4*>(reinterpret_cast<unsigned short*>(base) + idx) =
+        dj_u32x4{dj_pack2(lo.x, lo.y, dt), dj_pack2(lo.z, lo.w, dt), dj_pack2(hi.x, hi.y, dt), dj_pack2(hi.z, hi.w, dt)};
+  }
+}
+__device__ __forceinline__ f32x4 dj_mask4(f32x4 g, f32x4 m) {
+  g.x = (m.x > 0.f) ? g.x : 0.f;
+  g.y = (m.y > 0.f) ? g.y : 0.f;
+  g.z = (m.z > 0.f) ? g.z : 0.f;
+  g.w = (m.w > 0.f) ? g.w : 0.f;
+  return g;
+}
+
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static inline bool dt_known(int dt) { return dt == DJ_F32 || dt == DJ_F16 || dt == DJ_BF16; }
+// 4-element pieces legal: 16-byte aligned base (8 would do for 16-bit) and a pixel stride that is a multiple of 4 elements
+static inline bool vec_ok(const void* p, long ld) { return al16(p) && ld % 4 == 0; }
+
+// ---------------------------------------------------------------------------------
 // Blocked column reduction: out[blk][q][c] = sum over the block's rows of f_q(row, c), q in {0,1}
 // ---------------------------------------------------------------------------------
 // Every functor maps (row, first column of a group of VEC) -> two per-column contributions.
@@ -40,13 +135,14 @@ struct ColStatsF {  // (x, x^2)
 
 // dy masked by a ReLU, and dy*xhat.  mask_mode 0: none; 1: relu output tensor `y` > 0;
 // 2: own affine z*scale+shift > 0.
+template <bool TYPED>
 struct BnBwdF {
-  const float* dy;
-  int ld_dy;
-  const float* z;
-  int ld_z;
-  const float* y;
-  int ld_y;
+  const void* dy;
+  int dt_dy, ld_dy;
+  const void* z;
+  int dt_z, ld_z;
+  const void* y;
+  int dt_y, ld_y;
   const float* mean;
   const float* invstd;
   const float* scale;
@@ -55,17 +151,14 @@ struct BnBwdF {
   template <int VEC>
   __device__ __forceinline__ void eval(long r, int c, f32x4& v0, f32x4& v1) const {
     using IO = VecIO<VEC>;
-    f32x4 g = IO::ld(dy + r * ld_dy + c);
-    f32x4 zz = IO::ld(z + r * ld_z + c);
+    f32x4 g = dj_ldt<VEC, TYPED>(dy, r * ld_dy + c, dt_dy);
+    f32x4 zz = dj_ldt<VEC, TYPED>(z, r * ld_z + c, dt_z);
     f32x4 m = {1.f, 1.f, 1.f, 1.f};
     if (mask_mode == 1)
-      m = IO::ld(y + r * ld_y + c);
+      m = dj_ldt<VEC, TYPED>(y, r * ld_y + c, dt_y);
     else if (mask_mode == 2)
       m = zz * IO::ld(scale + c) + IO::ld(shift + c);
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
+    g = dj_mask4(g, m);
     v0 = g;
     v1 = g * (zz - IO::ld(mean + c)) * IO::ld(invstd + c);
   }
@@ -144,8 +237,6 @@ static int launch_colreduce(F f, long rows, int C, bool vec4, float* partial, hi
   return DJ_OK;
 }
 
-static inline bool al16p(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // Column sums of the two partial slots for DJ_FIN_CH channels per block: 1024 threads = 16 channels x 64 row lanes
 // (a 38x38x256 layer has 722 partial rows but only 256 channels: few channels per block keeps 16 blocks busy and
 // 12 rows per lane), 64-byte row segments, double accumulation.  Valid in threads with ty == 0 (c < C).
@@ -222,14 +313,14 @@ extern "C" int dj_reduce_rows(long rows) { return dj_cdiv(rows, DJ_RB); }
 extern "C" int dj_colstats_partial(const float* x, long rows, int C, int ld, float* partial, void* stream) {
   DJ_CHECK_ARG(x && partial && rows > 0 && C > 0 && ld >= C, "colstats: bad arguments");
   ColStatsF f{x, ld};
-  bool v4 = C % 4 == 0 && ld % 4 == 0 && al16p(x) && al16p(partial);
+  bool v4 = C % 4 == 0 && ld % 4 == 0 && al16(x) && al16(partial);
   return launch_colreduce(f, rows, C, v4, partial, (hipStream_t)stream, "dj_colstats_partial");
 }
 
 extern "C" int dj_colsum_partial(const float* dy, long rows, int C, int ld, float* partial, void* stream) {
   DJ_CHECK_ARG(dy && partial && rows > 0 && C > 0 && ld >= C, "colsum: bad arguments");
   ColSumF f{dy, ld};
-  bool v4 = C % 4 == 0 && ld % 4 == 0 && al16p(dy) && al16p(partial);
+  bool v4 = C % 4 == 0 && ld % 4 == 0 && al16(dy) && al16(partial);
   return launch_colreduce(f, rows, C, v4, partial, (hipStream_t)stream, "dj_colsum_partial");
 }
 
@@ -394,10 +485,10 @@ extern "C" int dj_bn_infer_coeffs(const float* gamma, const float* beta, const f
 // ---------------------------------------------------------------------------------
 // y = act(x*scale + shift [+ res*res_scale + res_shift]); scale/shift may be null (identity)
 // ---------------------------------------------------------------------------------
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_affine_act_kernel(const float* x, int ldx, const float* scale,
-                                                             const float* shift, const float* res, int ldres,
-                                                             const float* rscale, const float* rshift, float* y,
+template <int VEC, bool TYPED>
+__global__ __launch_bounds__(256) void dj_affine_act_kernel(const void* x, int dt_x, int ldx, const float* scale,
+                                                             const float* shift, const void* res, int dt_res, int ldres,
+                                                             const float* rscale, const float* rshift, void* y, int dt_y,
                                                              int ldy, long rows, int C, int relu) {
   using IO = VecIO<VEC>;
   const int cv = C / VEC;
@@ -406,10 +497,10 @@ __global__ __launch_bounds__(256) void dj_affine_act_kernel(const float* x, int 
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     long r = i / cv;
     int c = (int)(i - r * cv) * VEC;
-    f32x4 v = IO::ld(x + r * ldx + c);
+    f32x4 v = dj_ldt<VEC, TYPED>(x, r * ldx + c, dt_x);
     if (scale) v = v * IO::ld(scale + c) + IO::ld(shift + c);
     if (res) {
-      f32x4 t = IO::ld(res + r * ldres + c);
+      f32x4 t = dj_ldt<VEC, TYPED>(res, r * ldres + c, dt_res);
       if (rscale) t = t * IO::ld(rscale + c) + IO::ld(rshift + c);
       v += t;
     }
@@ -417,52 +508,88 @@ __global__ __launch_bounds__(256) void dj_affine_act_kernel(const float* x, int 
     v.y = fmaxf(v.y, floor_);
     v.z = fmaxf(v.z, floor_);
     v.w = fmaxf(v.w, floor_);
-    IO::st(y + r * ldy + c, v);
+    dj_stt<VEC, TYPED>(y, r * ldy + c, dt_y, v);
   }
 }
-
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 static inline int ew_blocks(long total) {
   long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-extern "C" int dj_affine_act(const float* x, int ldx, const float* scale, const float* shift, const float* res,
-                             int ldres, const float* res_scale, const float* res_shift, float* y, int ldy,
-                             long rows, int C, int relu, void* stream) {
+// KERNEL<4, TYPED> over groups of four columns when `v4`, KERNEL<1, TYPED> over single elements otherwise
+#define DJ_LAUNCH_EW(KERNEL, TYPED, v4, rows, cols, s, ...)                                                             \
+  do {                                                                                                                  \
+    if (v4)                                                                                                             \
+      hipLaunchKernelGGL((KERNEL<4, TYPED>), dim3(ew_blocks((rows) * ((cols) / 4))), dim3(256), 0, s, __VA_ARGS__);     \
+    else                                                                                                                \
+      hipLaunchKernelGGL((KERNEL<1, TYPED>), dim3(ew_blocks((rows) * (cols))), dim3(256), 0, s, __VA_ARGS__);           \
+  } while (0)
+
+// One host body per pass: TYPED = false behind the float entry point (every code DJ_F32), true behind the `_t` one;
+// `name` is the entry point's, for the launch error.
+template <bool TYPED>
+static int affine_act_impl(const char* name, const void* x, int dt_x, int ldx, const float* scale, const float* shift,
+                           const void* res, int dt_res, int ldres, const float* res_scale, const float* res_shift, void* y,
+                           int dt_y, int ldy, long rows, int C, int relu, void* stream) {
   DJ_CHECK_ARG(x && y && rows > 0 && C > 0 && ldx >= C && ldy >= C, "affine_act: bad arguments");
+  DJ_CHECK_ARG(dt_known(dt_x) && dt_known(dt_y) && (!res || dt_known(dt_res)), "affine_act: unknown storage type");
   DJ_CHECK_ARG((scale == nullptr) == (shift == nullptr) && (res_scale == nullptr) == (res_shift == nullptr),
                "affine_act: scale/shift come together");
   DJ_CHECK_ARG(res || !res_scale, "affine_act: res_scale without res");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (!res || ldres % 4 == 0) && al16(x) && al16(y) &&
-            al16(res) && al16(scale) && al16(shift) && al16(res_scale) && al16(res_shift);
-  if (v4) {
-    hipLaunchKernelGGL(dj_affine_act_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, x, ldx, scale, shift,
-                       res, ldres, res_scale, res_shift, y, ldy, rows, C, relu);
-  } else {
-    hipLaunchKernelGGL(dj_affine_act_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, x, ldx, scale, shift, res,
-                       ldres, res_scale, res_shift, y, ldy, rows, C, relu);
-  }
-  DJ_CHECK_LAUNCH("dj_affine_act");
+  bool v4 = (C % 4 == 0) && vec_ok(x, ldx) && vec_ok(y, ldy) && (!res || vec_ok(res, ldres)) && al16(scale) && al16(shift) &&
+            al16(res_scale) && al16(res_shift);
+  DJ_LAUNCH_EW(dj_affine_act_kernel, TYPED, v4, rows, C, (hipStream_t)stream, x, dt_x, ldx, scale, shift, res, dt_res, ldres,
+               res_scale, res_shift, y, dt_y, ldy, rows, C, relu);
+  DJ_CHECK_LAUNCH(name);
   return DJ_OK;
+}
+
+extern "C" int dj_affine_act(const float* x, int ldx, const float* scale, const float* shift, const float* res,
+                             int ldres, const float* res_scale, const float* res_shift, float* y, int ldy,
+                             long rows, int C, int relu, void* stream) {
+  return affine_act_impl<false>("dj_affine_act", x, DJ_F32, ldx, scale, shift, res, DJ_F32, ldres, res_scale, res_shift, y,
+                                DJ_F32, ldy, rows, C, relu, stream);
+}
+
+extern "C" int dj_affine_act_t(const void* x, int dt_x, int ldx, const float* scale, const float* shift, const void* res,
+                               int dt_res, int ldres, const float* res_scale, const float* res_shift, void* y, int dt_y,
+                               int ldy, long rows, int C, int relu, void* stream) {
+  return affine_act_impl<true>("dj_affine_act_t", x, dt_x, ldx, scale, shift, res, dt_res, ldres, res_scale, res_shift, y,
+                               dt_y, ldy, rows, C, relu, stream);
 }
 
 // ---------------------------------------------------------------------------------
 // BatchNormalization backward
 // ---------------------------------------------------------------------------------
-extern "C" int dj_bn_bwd_reduce(const float* dy, int ld_dy, const float* z, int ld_z, const float* y, int ld_y,
-                                const float* mean, const float* invstd, const float* scale, const float* shift,
-                                int mask_mode, long rows, int C, float* partial, void* stream) {
+template <bool TYPED>
+static int bn_bwd_reduce_impl(const char* name, const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z,
+                              const void* y, int dt_y, int ld_y, const float* mean, const float* invstd, const float* scale,
+                              const float* shift, int mask_mode, long rows, int C, float* partial, void* stream) {
   DJ_CHECK_ARG(dy && z && mean && invstd && partial && rows > 0 && C > 0, "bn_bwd_reduce: bad arguments");
+  DJ_CHECK_ARG(dt_known(dt_dy) && dt_known(dt_z) && (mask_mode != 1 || dt_known(dt_y)), "bn_bwd_reduce: unknown storage type");
   DJ_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "bn_bwd_reduce: mask_mode");
   DJ_CHECK_ARG(mask_mode != 1 || y, "bn_bwd_reduce: mask_mode 1 needs y");
   DJ_CHECK_ARG(mask_mode != 2 || (scale && shift), "bn_bwd_reduce: mask_mode 2 needs scale/shift");
-  BnBwdF f{dy, ld_dy, z, ld_z, y, ld_y, mean, invstd, scale, shift, mask_mode};
-  bool v4 = C % 4 == 0 && ld_dy % 4 == 0 && ld_z % 4 == 0 && (mask_mode != 1 || ld_y % 4 == 0) && al16p(dy) && al16p(z) &&
-            al16p(y) && al16p(mean) && al16p(invstd) && al16p(scale) && al16p(shift) && al16p(partial);
-  return launch_colreduce(f, rows, C, v4, partial, (hipStream_t)stream, "dj_bn_bwd_reduce");
+  BnBwdF<TYPED> f{dy, dt_dy, ld_dy, z, dt_z, ld_z, y, dt_y, ld_y, mean, invstd, scale, shift, mask_mode};
+  // the order of the sums depends on this choice; y counts only where it is read
+  bool v4 = C % 4 == 0 && vec_ok(dy, ld_dy) && vec_ok(z, ld_z) && (mask_mode != 1 || vec_ok(y, ld_y)) && al16(mean) &&
+            al16(invstd) && al16(scale) && al16(shift) && al16(partial);
+  return launch_colreduce(f, rows, C, v4, partial, (hipStream_t)stream, name);
+}
+
+extern "C" int dj_bn_bwd_reduce(const float* dy, int ld_dy, const float* z, int ld_z, const float* y, int ld_y,
+                                const float* mean, const float* invstd, const float* scale, const float* shift,
+                                int mask_mode, long rows, int C, float* partial, void* stream) {
+  return bn_bwd_reduce_impl<false>("dj_bn_bwd_reduce", dy, DJ_F32, ld_dy, z, DJ_F32, ld_z, y, DJ_F32, ld_y, mean, invstd, scale,
+                                   shift, mask_mode, rows, C, partial, stream);
+}
+
+extern "C" int dj_bn_bwd_reduce_t(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z, const void* y,
+                                  int dt_y, int ld_y, const float* mean, const float* invstd, const float* scale,
+                                  const float* shift, int mask_mode, long rows, int C, float* partial, void* stream) {
+  return bn_bwd_reduce_impl<true>("dj_bn_bwd_reduce_t", dy, dt_dy, ld_dy, z, dt_z, ld_z, y, dt_y, ld_y, mean, invstd, scale,
+                                  shift, mask_mode, rows, C, partial, stream);
 }
 
 // dgamma, dbeta and the coefficients of dz = k0*dy_masked + k1*z + k2
@@ -493,311 +620,32 @@ extern "C" int dj_bn_bwd_finalize(const float* partial, int nrows, long count, c
   return DJ_OK;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_bn_bwd_apply_kernel(const float* dy, int ld_dy, const float* z, int ld_z,
-                                                               const float* y, int ld_y, const float* scale,
-                                                               const float* shift, int mask_mode, const float* k0,
-                                                               const float* k1, const float* k2, float* dz, int ld_dz,
-                                                               long rows, int C, float* dmasked, int ld_dm,
-                                                               int dm_beta) {
+template <int VEC, bool TYPED>
+__global__ __launch_bounds__(256) void dj_bn_bwd_apply_kernel(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z,
+                                                               int ld_z, const void* y, int dt_y, int ld_y,
+                                                               const float* scale, const float* shift, int mask_mode,
+                                                               const float* k0, const float* k1, const float* k2, void* dz,
+                                                               int dt_dz, int ld_dz, long rows, int C, void* dmasked,
+                                                               int dt_dm, int ld_dm, int dm_beta) {
   using IO = VecIO<VEC>;
   const int cv = C / VEC;
   long total = rows * cv;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     long r = i / cv;
     int c = (int)(i - r * cv) * VEC;
-    f32x4 g = IO::ld(dy + r * ld_dy + c);
-    f32x4 zz = IO::ld(z + r * ld_z + c);
+    f32x4 g = dj_ldt<VEC, TYPED>(dy, r * ld_dy + c, dt_dy);
+    f32x4 zz = dj_ldt<VEC, TYPED>(z, r * ld_z + c, dt_z);
     f32x4 m = {1.f, 1.f, 1.f, 1.f};
     if (mask_mode == 1) {
-      m = IO::ld(y + r * ld_y + c);
+      m = dj_ldt<VEC, TYPED>(y, r * ld_y + c, dt_y);
     } else if (mask_mode == 2) {
       m = zz * IO::ld(scale + c) + IO::ld(shift + c);
     }
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
-    IO::st(dz + r * ld_dz + c, IO::ld(k0 + c) * g + IO::ld(k1 + c) * zz + IO::ld(k2 + c));
-    if (dmasked) {   // the masked upstream gradient is also the identity shortcut's gradient (Add + ReLU backward)
-      float* d = dmasked + r * ld_dm + c;
-      IO::st(d, dm_beta ? g + IO::ld(d) : g);
-    }
-  }
-}
-
-extern "C" int dj_bn_bwd_apply(const float* dy, int ld_dy, const float* z, int ld_z, const float* y, int ld_y,
-                               const float* scale, const float* shift, int mask_mode, const float* k0,
-                               const float* k1, const float* k2, float* dz, int ld_dz, long rows, int C,
-                               float* dmasked, int ld_dm, int dm_beta, void* stream) {
-  DJ_CHECK_ARG(dy && z && k0 && k1 && k2 && dz && rows > 0 && C > 0, "bn_bwd_apply: bad arguments");
-  DJ_CHECK_ARG(!dmasked || ld_dm >= C, "bn_bwd_apply: ld_dm < C");
-  DJ_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "bn_bwd_apply: mask_mode");
-  DJ_CHECK_ARG(mask_mode != 1 || y, "bn_bwd_apply: mask_mode 1 needs y");
-  DJ_CHECK_ARG(mask_mode != 2 || (scale && shift), "bn_bwd_apply: mask_mode 2 needs scale/shift");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (C % 4 == 0) && (ld_dy % 4 == 0) && (ld_z % 4 == 0) && (ld_dz % 4 == 0) && (mask_mode != 1 || ld_y % 4 == 0) &&
-            al16(dy) && al16(z) && al16(dz) && al16(y) && al16(scale) && al16(shift) && al16(k0) && al16(k1) && al16(k2) &&
-            al16(dmasked) && (!dmasked || ld_dm % 4 == 0);
-  if (v4)
-    hipLaunchKernelGGL(dj_bn_bwd_apply_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, dy, ld_dy, z, ld_z,
-                       y, ld_y, scale, shift, mask_mode, k0, k1, k2, dz, ld_dz, rows, C, dmasked, ld_dm, dm_beta);
-  else
-    hipLaunchKernelGGL(dj_bn_bwd_apply_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dy, ld_dy, z, ld_z, y,
-                       ld_y, scale, shift, mask_mode, k0, k1, k2, dz, ld_dz, rows, C, dmasked, ld_dm, dm_beta);
-  DJ_CHECK_LAUNCH("dj_bn_bwd_apply");
-  return DJ_OK;
-}
-
-// dx (+)= dy * [y > 0]
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_relu_bwd_kernel(const float* dy, int ld_dy, const float* y, int ld_y,
-                                                           float* dx, int ld_dx, long rows, int C, int beta) {
-  using IO = VecIO<VEC>;
-  const int cv = C / VEC;
-  long total = rows * cv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long r = i / cv;
-    int c = (int)(i - r * cv) * VEC;
-    f32x4 g = IO::ld(dy + r * ld_dy + c);
-    f32x4 m = IO::ld(y + r * ld_y + c);
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
-    float* d = dx + r * ld_dx + c;
-    if (beta) g += IO::ld(d);
-    IO::st(d, g);
-  }
-}
-
-extern "C" int dj_relu_bwd(const float* dy, int ld_dy, const float* y, int ld_y, float* dx, int ld_dx, long rows,
-                           int C, int beta, void* stream) {
-  DJ_CHECK_ARG(dy && y && dx && rows > 0 && C > 0, "relu_bwd: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (C % 4 == 0) && (ld_dy % 4 == 0) && (ld_y % 4 == 0) && (ld_dx % 4 == 0) && al16(dy) && al16(y) && al16(dx);
-  if (v4)
-    hipLaunchKernelGGL(dj_relu_bwd_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, dy, ld_dy, y, ld_y, dx,
-                       ld_dx, rows, C, beta);
-  else
-    hipLaunchKernelGGL(dj_relu_bwd_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dy, ld_dy, y, ld_y, dx, ld_dx,
-                       rows, C, beta);
-  DJ_CHECK_LAUNCH("dj_relu_bwd");
-  return DJ_OK;
-}
-
-// ---------------------------------------------------------------------------------
-// The same elementwise passes over tensors that carry their storage type (round 3, BASELINE config 5: activations held as
-// fp16 and their gradients as bf16 in HBM inside the backbone, fp32 elsewhere): every tensor operand comes with a type
-// code (DJ_F32 / DJ_F16 / DJ_BF16), looked at per access with a wave-uniform branch -- these passes are HBM-bound, the
-// branch is free -- and all arithmetic stays fp32.  A 4-element piece of a 16-bit tensor is one 8-byte access.
-// ---------------------------------------------------------------------------------
-typedef unsigned int dj_u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 dj_h4 __attribute__((ext_vector_type(4)));
-
-template <int VEC>
-__device__ __forceinline__ f32x4 dj_ldt(const void* base, long idx, int dt) {
-  if (dt == DJ_F32) return VecIO<VEC>::ld(reinterpret_cast<const float*>(base) + idx);
-  if (VEC == 4) {
-    const dj_u32x2 v = *reinterpret_cast<const dj_u32x2*>(reinterpret_cast<const unsigned short*>(base) + idx);
-    if (dt == DJ_F16) {
-      const dj_h4 h = __builtin_bit_cast(dj_h4, v);
-      return f32x4{(float)h.x, (float)h.y, (float)h.z, (float)h.w};
-    }
-    return f32x4{__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xFFFF0000u),
-                 __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xFFFF0000u)};
-  }
-  const unsigned short u = reinterpret_cast<const unsigned short*>(base)[idx];
-  const float f = (dt == DJ_F16) ? (float)__builtin_bit_cast(_Float16, u) : __builtin_bit_cast(float, (unsigned)u << 16);
-  return f32x4{f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ unsigned dj_pack2(float lo, float hi, int dt) {
-  if (dt == DJ_F16) {
-    const _Float16 a = (_Float16)lo, b = (_Float16)hi;
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-  }
-  const __bf16 a = (__bf16)lo, b = (__bf16)hi;   // round to nearest even
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-
-template <int VEC>
-__device__ __forceinline__ void dj_stt(void* base, long idx, int dt, f32x4 v) {
-  if (dt == DJ_F32) {
-    VecIO<VEC>::st(reinterpret_cast<float*>(base) + idx, v);
-  } else if (VEC == 4) {
-    *reinterpret_cast<dj_u32x2*>(reinterpret_cast<unsigned short*>(base) + idx) = dj_u32x2{dj_pack2(v.x, v.y, dt), dj_pack2(v.z, v.w, dt)};
-  } else {
-    reinterpret_cast<unsigned short*>(base)[idx] = (unsigned short)(dj_pack2(v.x, 0.f, dt) & 0xFFFFu);
-  }
-}
-
-// eight consecutive elements: ONE 16-byte access of a 16-bit tensor (two of a fp32 one) -- twice the bytes in flight per
-// thread of the 4-element form, which is what these HBM-bound passes are short of when every tensor is 16 bits wide
-typedef unsigned int dj_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 dj_h8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void dj_ld8(const void* base, long idx, int dt, f32x4& lo, f32x4& hi) {
-  if (dt == DJ_F32) {
-    lo = VecIO<4>::ld(reinterpret_cast<const float*>(base) + idx);
-    hi = VecIO<4>::ld(reinterpret_cast<const float*>(base) + idx + 4);
-    return;
-  }
-  const dj_u32x4 v = *reinterpret_cast<const dj_u32x4*>(reinterpret_cast<const unsigned short*>(base) + idx);
-  if (dt == DJ_F16) {
-    const dj_h8 h = __builtin_bit_cast(dj_h8, v);
-    lo = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-    hi = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
-  } else {
-    lo = f32x4{__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xFFFF0000u),
-               __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xFFFF0000u)};
-    hi = f32x4{__builtin_bit_cast(float, v.z << 16), __builtin_bit_cast(float, v.z & 0xFFFF0000u),
-               __builtin_bit_cast(float, v.w << 16), __builtin_bit_cast(float, v.w & 0xFFFF0000u)};
-  }
-}
-__device__ __forceinline__ void dj_st8(void* base, long idx, int dt, f32x4 lo, f32x4 hi) {
-  if (dt == DJ_F32) {
-    VecIO<4>::st(reinterpret_cast<float*>(base) + idx, lo);
-    VecIO<4>::st(reinterpret_cast<float*>(base) + idx + 4, hi);
-  } else {
-    *reinterpret_cast<dj_u32x4*>(reinterpret_cast<unsigned short*>(base) + idx) =
-        dj_u32x4{dj_pack2(lo.x, lo.y, dt), dj_pack2(lo.z, lo.w, dt), dj_pack2(hi.x, hi.y, dt), dj_pack2(hi.z, hi.w, dt)};
-  }
-}
-__device__ __forceinline__ f32x4 dj_mask4(f32x4 g, f32x4 m) {
-  g.x = (m.x > 0.f) ? g.x : 0.f;
-  g.y = (m.y > 0.f) ? g.y : 0.f;
-  g.z = (m.z > 0.f) ? g.z : 0.f;
-  g.w = (m.w > 0.f) ? g.w : 0.f;
-  return g;
-}
-
-static inline bool dt_known(int dt) { return dt == DJ_F32 || dt == DJ_F16 || dt == DJ_BF16; }
-// 4-element pieces legal: 16-byte aligned base (8 would do for 16-bit) and a pixel stride that is a multiple of 4 elements
-static inline bool vec_ok(const void* p, long ld) { return al16(p) && ld % 4 == 0; }
-
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_affine_act_t_kernel(const void* x, int dt_x, int ldx, const float* scale,
-                                                               const float* shift, const void* res, int dt_res, int ldres,
-                                                               const float* rscale, const float* rshift, void* y, int dt_y,
-                                                               int ldy, long rows, int C, int relu) {
-  using IO = VecIO<VEC>;
-  const int cv = C / VEC;
-  long total = rows * cv;
-  const float floor_ = relu ? 0.f : -INFINITY;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long r = i / cv;
-    int c = (int)(i - r * cv) * VEC;
-    f32x4 v = dj_ldt<VEC>(x, r * ldx + c, dt_x);
-    if (scale) v = v * IO::ld(scale + c) + IO::ld(shift + c);
-    if (res) {
-      f32x4 t = dj_ldt<VEC>(res, r * ldres + c, dt_res);
-      if (rscale) t = t * IO::ld(rscale + c) + IO::ld(rshift + c);
-      v += t;
-    }
-    v.x = fmaxf(v.x, floor_);
-    v.y = fmaxf(v.y, floor_);
-    v.z = fmaxf(v.z, floor_);
-    v.w = fmaxf(v.w, floor_);
-    dj_stt<VEC>(y, r * ldy + c, dt_y, v);
-  }
-}
-
-extern "C" int dj_affine_act_t(const void* x, int dt_x, int ldx, const float* scale, const float* shift, const void* res,
-                               int dt_res, int ldres, const float* res_scale, const float* res_shift, void* y, int dt_y,
-                               int ldy, long rows, int C, int relu, void* stream) {
-  DJ_CHECK_ARG(x && y && rows > 0 && C > 0 && ldx >= C && ldy >= C, "affine_act: bad arguments");
-  DJ_CHECK_ARG(dt_known(dt_x) && dt_known(dt_y) && (!res || dt_known(dt_res)), "affine_act: unknown storage type");
-  DJ_CHECK_ARG((scale == nullptr) == (shift == nullptr) && (res_scale == nullptr) == (res_shift == nullptr),
-               "affine_act: scale/shift come together");
-  DJ_CHECK_ARG(res || !res_scale, "affine_act: res_scale without res");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (C % 4 == 0) && vec_ok(x, ldx) && vec_ok(y, ldy) && (!res || vec_ok(res, ldres)) && al16(scale) && al16(shift) &&
-            al16(res_scale) && al16(res_shift);
-  if (v4)
-    hipLaunchKernelGGL(dj_affine_act_t_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, x, dt_x, ldx, scale, shift,
-                       res, dt_res, ldres, res_scale, res_shift, y, dt_y, ldy, rows, C, relu);
-  else
-    hipLaunchKernelGGL(dj_affine_act_t_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, x, dt_x, ldx, scale, shift, res,
-                       dt_res, ldres, res_scale, res_shift, y, dt_y, ldy, rows, C, relu);
-  DJ_CHECK_LAUNCH("dj_affine_act_t");
-  return DJ_OK;
-}
-
-// BnBwdF over typed tensors
-struct BnBwdTF {
-  const void* dy;
-  int dt_dy, ld_dy;
-  const void* z;
-  int dt_z, ld_z;
-  const void* y;
-  int dt_y, ld_y;
-  const float* mean;
-  const float* invstd;
-  const float* scale;
-  const float* shift;
-  int mask_mode;
-  template <int VEC>
-  __device__ __forceinline__ void eval(long r, int c, f32x4& v0, f32x4& v1) const {
-    using IO = VecIO<VEC>;
-    f32x4 g = dj_ldt<VEC>(dy, r * ld_dy + c, dt_dy);
-    f32x4 zz = dj_ldt<VEC>(z, r * ld_z + c, dt_z);
-    f32x4 m = {1.f, 1.f, 1.f, 1.f};
-    if (mask_mode == 1)
-      m = dj_ldt<VEC>(y, r * ld_y + c, dt_y);
-    else if (mask_mode == 2)
-      m = zz * IO::ld(scale + c) + IO::ld(shift + c);
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
-    v0 = g;
-    v1 = g * (zz - IO::ld(mean + c)) * IO::ld(invstd + c);
-  }
-};
-
-extern "C" int dj_bn_bwd_reduce_t(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z, const void* y,
-                                  int dt_y, int ld_y, const float* mean, const float* invstd, const float* scale,
-                                  const float* shift, int mask_mode, long rows, int C, float* partial, void* stream) {
-  DJ_CHECK_ARG(dy && z && mean && invstd && partial && rows > 0 && C > 0, "bn_bwd_reduce: bad arguments");
-  DJ_CHECK_ARG(dt_known(dt_dy) && dt_known(dt_z) && (mask_mode != 1 || dt_known(dt_y)), "bn_bwd_reduce: unknown storage type");
-  DJ_CHECK_ARG(mask_mode >= 0 && mask_mode <= 2, "bn_bwd_reduce: mask_mode");
-  DJ_CHECK_ARG(mask_mode != 1 || y, "bn_bwd_reduce: mask_mode 1 needs y");
-  DJ_CHECK_ARG(mask_mode != 2 || (scale && shift), "bn_bwd_reduce: mask_mode 2 needs scale/shift");
-  BnBwdTF f{dy, dt_dy, ld_dy, z, dt_z, ld_z, y, dt_y, ld_y, mean, invstd, scale, shift, mask_mode};
-  bool v4 = C % 4 == 0 && vec_ok(dy, ld_dy) && vec_ok(z, ld_z) && (mask_mode != 1 || vec_ok(y, ld_y)) && al16p(mean) &&
-            al16p(invstd) && al16p(scale) && al16p(shift) && al16p(partial);
-  return launch_colreduce(f, rows, C, v4, partial, (hipStream_t)stream, "dj_bn_bwd_reduce_t");
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_bn_bwd_apply_t_kernel(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z,
-                                                                 int ld_z, const void* y, int dt_y, int ld_y,
-                                                                 const float* scale, const float* shift, int mask_mode,
-                                                                 const float* k0, const float* k1, const float* k2, void* dz,
-                                                                 int dt_dz, int ld_dz, long rows, int C, void* dmasked,
-                                                                 int dt_dm, int ld_dm, int dm_beta) {
-  using IO = VecIO<VEC>;
-  const int cv = C / VEC;
-  long total = rows * cv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long r = i / cv;
-    int c = (int)(i - r * cv) * VEC;
-    f32x4 g = dj_ldt<VEC>(dy, r * ld_dy + c, dt_dy);
-    f32x4 zz = dj_ldt<VEC>(z, r * ld_z + c, dt_z);
-    f32x4 m = {1.f, 1.f, 1.f, 1.f};
-    if (mask_mode == 1) {
-      m = dj_ldt<VEC>(y, r * ld_y + c, dt_y);
-    } else if (mask_mode == 2) {
-      m = zz * IO::ld(scale + c) + IO::ld(shift + c);
-    }
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
-    dj_stt<VEC>(dz, r * ld_dz + c, dt_dz, IO::ld(k0 + c) * g + IO::ld(k1 + c) * zz + IO::ld(k2 + c));
+    g = dj_mask4(g, m);
+    dj_stt<VEC, TYPED>(dz, r * ld_dz + c, dt_dz, IO::ld(k0 + c) * g + IO::ld(k1 + c) * zz + IO::ld(k2 + c));
     if (dmasked) {   // the masked upstream gradient is also the identity shortcut's gradient (Add + ReLU backward)
       const long o = r * ld_dm + c;
-      dj_stt<VEC>(dmasked, o, dt_dm, dm_beta ? g + dj_ldt<VEC>(dmasked, o, dt_dm) : g);
+      dj_stt<VEC, TYPED>(dmasked, o, dt_dm, dm_beta ? g + dj_ldt<VEC, TYPED>(dmasked, o, dt_dm) : g);
     }
   }
 }
@@ -841,10 +689,11 @@ __global__ __launch_bounds__(256) void dj_bn_bwd_apply_t8_kernel(const void* dy,
   }
 }
 
-extern "C" int dj_bn_bwd_apply_t(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z, const void* y,
-                                 int dt_y, int ld_y, const float* scale, const float* shift, int mask_mode, const float* k0,
-                                 const float* k1, const float* k2, void* dz, int dt_dz, int ld_dz, long rows, int C,
-                                 void* dmasked, int dt_dm, int ld_dm, int dm_beta, void* stream) {
+template <bool TYPED>
+static int bn_bwd_apply_impl(const char* name, const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z,
+                             const void* y, int dt_y, int ld_y, const float* scale, const float* shift, int mask_mode,
+                             const float* k0, const float* k1, const float* k2, void* dz, int dt_dz, int ld_dz, long rows, int C,
+                             void* dmasked, int dt_dm, int ld_dm, int dm_beta, void* stream) {
   DJ_CHECK_ARG(dy && z && k0 && k1 && k2 && dz && rows > 0 && C > 0, "bn_bwd_apply: bad arguments");
   DJ_CHECK_ARG(dt_known(dt_dy) && dt_known(dt_z) && dt_known(dt_dz) && (mask_mode != 1 || dt_known(dt_y)) &&
                    (!dmasked || dt_known(dt_dm)),
@@ -856,92 +705,73 @@ extern "C" int dj_bn_bwd_apply_t(const void* dy, int dt_dy, int ld_dy, const voi
   hipStream_t s = (hipStream_t)stream;
   bool v4 = (C % 4 == 0) && vec_ok(dy, ld_dy) && vec_ok(z, ld_z) && vec_ok(dz, ld_dz) && (mask_mode != 1 || vec_ok(y, ld_y)) &&
             al16(scale) && al16(shift) && al16(k0) && al16(k1) && al16(k2) && (!dmasked || vec_ok(dmasked, ld_dm));
-  const bool v8 = v4 && (C % 8 == 0) && (ld_dy % 8 == 0) && (ld_z % 8 == 0) && (ld_dz % 8 == 0) &&
+  // the 8-element form is the `_t` entry point's only
+  const bool v8 = TYPED && v4 && (C % 8 == 0) && (ld_dy % 8 == 0) && (ld_z % 8 == 0) && (ld_dz % 8 == 0) &&
                   (mask_mode != 1 || ld_y % 8 == 0) && (!dmasked || ld_dm % 8 == 0);
   if (v8)
     hipLaunchKernelGGL(dj_bn_bwd_apply_t8_kernel, dim3(ew_blocks(rows * (C / 8))), dim3(256), 0, s, dy, dt_dy, ld_dy, z, dt_z,
                        ld_z, y, dt_y, ld_y, scale, shift, mask_mode, k0, k1, k2, dz, dt_dz, ld_dz, rows, C, dmasked, dt_dm,
                        ld_dm, dm_beta);
-  else if (v4)
-    hipLaunchKernelGGL(dj_bn_bwd_apply_t_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, dy, dt_dy, ld_dy, z, dt_z,
-                       ld_z, y, dt_y, ld_y, scale, shift, mask_mode, k0, k1, k2, dz, dt_dz, ld_dz, rows, C, dmasked, dt_dm,
-                       ld_dm, dm_beta);
   else
-    hipLaunchKernelGGL(dj_bn_bwd_apply_t_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dy, dt_dy, ld_dy, z, dt_z, ld_z,
-                       y, dt_y, ld_y, scale, shift, mask_mode, k0, k1, k2, dz, dt_dz, ld_dz, rows, C, dmasked, dt_dm, ld_dm,
-                       dm_beta);
-  DJ_CHECK_LAUNCH("dj_bn_bwd_apply_t");
+    DJ_LAUNCH_EW(dj_bn_bwd_apply_kernel, TYPED, v4, rows, C, s, dy, dt_dy, ld_dy, z, dt_z, ld_z, y, dt_y, ld_y, scale, shift,
+                 mask_mode, k0, k1, k2, dz, dt_dz, ld_dz, rows, C, dmasked, dt_dm, ld_dm, dm_beta);
+  DJ_CHECK_LAUNCH(name);
   return DJ_OK;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_relu_bwd_t_kernel(const void* dy, int dt_dy, int ld_dy, const void* y, int dt_y,
-                                                             int ld_y, void* dx, int dt_dx, int ld_dx, long rows, int C,
-                                                             int beta) {
+extern "C" int dj_bn_bwd_apply(const float* dy, int ld_dy, const float* z, int ld_z, const float* y, int ld_y,
+                               const float* scale, const float* shift, int mask_mode, const float* k0,
+                               const float* k1, const float* k2, float* dz, int ld_dz, long rows, int C,
+                               float* dmasked, int ld_dm, int dm_beta, void* stream) {
+  return bn_bwd_apply_impl<false>("dj_bn_bwd_apply", dy, DJ_F32, ld_dy, z, DJ_F32, ld_z, y, DJ_F32, ld_y, scale, shift, mask_mode,
+                                  k0, k1, k2, dz, DJ_F32, ld_dz, rows, C, dmasked, DJ_F32, ld_dm, dm_beta, stream);
+}
+
+extern "C" int dj_bn_bwd_apply_t(const void* dy, int dt_dy, int ld_dy, const void* z, int dt_z, int ld_z, const void* y,
+                                 int dt_y, int ld_y, const float* scale, const float* shift, int mask_mode, const float* k0,
+                                 const float* k1, const float* k2, void* dz, int dt_dz, int ld_dz, long rows, int C,
+                                 void* dmasked, int dt_dm, int ld_dm, int dm_beta, void* stream) {
+  return bn_bwd_apply_impl<true>("dj_bn_bwd_apply_t", dy, dt_dy, ld_dy, z, dt_z, ld_z, y, dt_y, ld_y, scale, shift, mask_mode, k0,
+                                 k1, k2, dz, dt_dz, ld_dz, rows, C, dmasked, dt_dm, ld_dm, dm_beta, stream);
+}
+
+// dx (+)= dy * [y > 0]
+template <int VEC, bool TYPED>
+__global__ __launch_bounds__(256) void dj_relu_bwd_kernel(const void* dy, int dt_dy, int ld_dy, const void* y, int dt_y,
+                                                           int ld_y, void* dx, int dt_dx, int ld_dx, long rows, int C,
+                                                           int beta) {
   const int cv = C / VEC;
   long total = rows * cv;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     long r = i / cv;
     int c = (int)(i - r * cv) * VEC;
-    f32x4 g = dj_ldt<VEC>(dy, r * ld_dy + c, dt_dy);
-    f32x4 m = dj_ldt<VEC>(y, r * ld_y + c, dt_y);
-    g.x = (m.x > 0.f) ? g.x : 0.f;
-    g.y = (m.y > 0.f) ? g.y : 0.f;
-    g.z = (m.z > 0.f) ? g.z : 0.f;
-    g.w = (m.w > 0.f) ? g.w : 0.f;
+    f32x4 g = dj_mask4(dj_ldt<VEC, TYPED>(dy, r * ld_dy + c, dt_dy), dj_ldt<VEC, TYPED>(y, r * ld_y + c, dt_y));
     const long o = r * ld_dx + c;
-    if (beta) g += dj_ldt<VEC>(dx, o, dt_dx);
-    dj_stt<VEC>(dx, o, dt_dx, g);
+    if (beta) g += dj_ldt<VEC, TYPED>(dx, o, dt_dx);
+    dj_stt<VEC, TYPED>(dx, o, dt_dx, g);
   }
+}
+
+template <bool TYPED>
+static int relu_bwd_impl(const char* name, const void* dy, int dt_dy, int ld_dy, const void* y, int dt_y, int ld_y, void* dx,
+                         int dt_dx, int ld_dx, long rows, int C, int beta, void* stream) {
+  DJ_CHECK_ARG(dy && y && dx && rows > 0 && C > 0, "relu_bwd: bad arguments");
+  DJ_CHECK_ARG(dt_known(dt_dy) && dt_known(dt_y) && dt_known(dt_dx), "relu_bwd: unknown storage type");
+  bool v4 = (C % 4 == 0) && vec_ok(dy, ld_dy) && vec_ok(y, ld_y) && vec_ok(dx, ld_dx);
+  DJ_LAUNCH_EW(dj_relu_bwd_kernel, TYPED, v4, rows, C, (hipStream_t)stream, dy, dt_dy, ld_dy, y, dt_y, ld_y, dx, dt_dx, ld_dx,
+               rows, C, beta);
+  DJ_CHECK_LAUNCH(name);
+  return DJ_OK;
+}
+
+extern "C" int dj_relu_bwd(const float* dy, int ld_dy, const float* y, int ld_y, float* dx, int ld_dx, long rows,
+                           int C, int beta, void* stream) {
+  return relu_bwd_impl<false>("dj_relu_bwd", dy, DJ_F32, ld_dy, y, DJ_F32, ld_y, dx, DJ_F32, ld_dx, rows, C, beta, stream);
 }
 
 extern "C" int dj_relu_bwd_t(const void* dy, int dt_dy, int ld_dy, const void* y, int dt_y, int ld_y, void* dx, int dt_dx,
                              int ld_dx, long rows, int C, int beta, void* stream) {
-  DJ_CHECK_ARG(dy && y && dx && rows > 0 && C > 0, "relu_bwd: bad arguments");
-  DJ_CHECK_ARG(dt_known(dt_dy) && dt_known(dt_y) && dt_known(dt_dx), "relu_bwd: unknown storage type");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (C % 4 == 0) && vec_ok(dy, ld_dy) && vec_ok(y, ld_y) && vec_ok(dx, ld_dx);
-  if (v4)
-    hipLaunchKernelGGL(dj_relu_bwd_t_kernel<4>, dim3(ew_blocks(rows * (C / 4))), dim3(256), 0, s, dy, dt_dy, ld_dy, y, dt_y,
-                       ld_y, dx, dt_dx, ld_dx, rows, C, beta);
-  else
-    hipLaunchKernelGGL(dj_relu_bwd_t_kernel<1>, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dy, dt_dy, ld_dy, y, dt_y, ld_y, dx,
-                       dt_dx, ld_dx, rows, C, beta);
-  DJ_CHECK_LAUNCH("dj_relu_bwd_t");
-  return DJ_OK;
-}
-
-// dst[r][c] (+)= src[r][c] with a change of storage type on the way (a 16-bit backbone tensor handed to a layer that
-// works on fp32, the gradient coming back)
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_copy2d_t_kernel(const void* src, int dt_src, long lds, void* dst, int dt_dst,
-                                                           long ldd, long rows, long cols, int beta) {
-  const long cv = cols / VEC;
-  long total = rows * cv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long r = i / cv;
-    long c = (i - r * cv) * VEC;
-    f32x4 v = dj_ldt<VEC>(src, r * lds + c, dt_src);
-    const long o = r * ldd + c;
-    if (beta) v += dj_ldt<VEC>(dst, o, dt_dst);
-    dj_stt<VEC>(dst, o, dt_dst, v);
-  }
-}
-
-extern "C" int dj_copy2d_t(const void* src, int dt_src, long ld_src, void* dst, int dt_dst, long ld_dst, long rows, long cols,
-                           int beta, void* stream) {
-  DJ_CHECK_ARG(src && dst && rows > 0 && cols > 0 && ld_src >= cols && ld_dst >= cols, "copy2d: bad arguments");
-  DJ_CHECK_ARG(dt_known(dt_src) && dt_known(dt_dst), "copy2d: unknown storage type");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (cols % 4 == 0) && vec_ok(src, ld_src) && vec_ok(dst, ld_dst);
-  if (v4)
-    hipLaunchKernelGGL(dj_copy2d_t_kernel<4>, dim3(ew_blocks(rows * (cols / 4))), dim3(256), 0, s, src, dt_src, ld_src, dst,
-                       dt_dst, ld_dst, rows, cols, beta);
-  else
-    hipLaunchKernelGGL(dj_copy2d_t_kernel<1>, dim3(ew_blocks(rows * cols)), dim3(256), 0, s, src, dt_src, ld_src, dst, dt_dst,
-                       ld_dst, rows, cols, beta);
-  DJ_CHECK_LAUNCH("dj_copy2d_t");
-  return DJ_OK;
+  return relu_bwd_impl<true>("dj_relu_bwd_t", dy, dt_dy, ld_dy, y, dt_y, ld_y, dx, dt_dx, ld_dx, rows, C, beta, stream);
 }
 
 // w16[i] = fp16(w[i]), wbf[i] = bf16(w[i]): the per-step 16-bit shadows of the fp32 master weights that the reduced-
@@ -950,8 +780,8 @@ extern "C" int dj_copy2d_t(const void* src, int dt_src, long ld_src, void* dst, 
 __global__ __launch_bounds__(256) void dj_shadow_weights_kernel(const float* w, void* w16, void* wbf, long n4) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const f32x4 v = VecIO<4>::ld(w + 4 * i);
-    if (w16) dj_stt<4>(w16, 4 * i, DJ_F16, v);
-    if (wbf) dj_stt<4>(wbf, 4 * i, DJ_BF16, v);
+    if (w16) dj_stt<4, true>(w16, 4 * i, DJ_F16, v);
+    if (wbf) dj_stt<4, true>(wbf, 4 * i, DJ_BF16, v);
   }
 }
 
@@ -963,36 +793,43 @@ extern "C" int dj_shadow_weights(const float* w, void* w16, void* wbf, long n, v
   return DJ_OK;
 }
 
-// dst[r][c] (+)= src[r][c]   (Concatenate / its gradient / Reshape+Concatenate(axis=1))
-template <int VEC>
-__global__ __launch_bounds__(256) void dj_copy2d_kernel(const float* src, long lds, float* dst, long ldd, long rows,
-                                                         long cols, int beta) {
-  using IO = VecIO<VEC>;
+// dst[r][c] (+)= src[r][c]   (Concatenate / its gradient / Reshape+Concatenate(axis=1)); TYPED: with a change of storage
+// type on the way (a 16-bit backbone tensor handed to a layer that works on fp32, the gradient coming back)
+template <int VEC, bool TYPED>
+__global__ __launch_bounds__(256) void dj_copy2d_kernel(const void* src, int dt_src, long lds, void* dst, int dt_dst,
+                                                         long ldd, long rows, long cols, int beta) {
   const long cv = cols / VEC;
   long total = rows * cv;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     long r = i / cv;
     long c = (i - r * cv) * VEC;
-    f32x4 v = IO::ld(src + r * lds + c);
-    float* d = dst + r * ldd + c;
-    if (beta) v += IO::ld(d);
-    IO::st(d, v);
+    f32x4 v = dj_ldt<VEC, TYPED>(src, r * lds + c, dt_src);
+    const long o = r * ldd + c;
+    if (beta) v += dj_ldt<VEC, TYPED>(dst, o, dt_dst);
+    dj_stt<VEC, TYPED>(dst, o, dt_dst, v);
   }
+}
+
+template <bool TYPED>
+static int copy2d_impl(const char* name, const void* src, int dt_src, long ld_src, void* dst, int dt_dst, long ld_dst, long rows,
+                       long cols, int beta, void* stream) {
+  DJ_CHECK_ARG(src && dst && rows > 0 && cols > 0 && ld_src >= cols && ld_dst >= cols, "copy2d: bad arguments");
+  DJ_CHECK_ARG(dt_known(dt_src) && dt_known(dt_dst), "copy2d: unknown storage type");
+  bool v4 = (cols % 4 == 0) && vec_ok(src, ld_src) && vec_ok(dst, ld_dst);
+  DJ_LAUNCH_EW(dj_copy2d_kernel, TYPED, v4, rows, cols, (hipStream_t)stream, src, dt_src, ld_src, dst, dt_dst, ld_dst, rows,
+               cols, beta);
+  DJ_CHECK_LAUNCH(name);
+  return DJ_OK;
 }
 
 extern "C" int dj_copy2d(const float* src, long ld_src, float* dst, long ld_dst, long rows, long cols, int beta,
                          void* stream) {
-  DJ_CHECK_ARG(src && dst && rows > 0 && cols > 0 && ld_src >= cols && ld_dst >= cols, "copy2d: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  bool v4 = (cols % 4 == 0) && (ld_src % 4 == 0) && (ld_dst % 4 == 0) && al16(src) && al16(dst);
-  if (v4)
-    hipLaunchKernelGGL(dj_copy2d_kernel<4>, dim3(ew_blocks(rows * (cols / 4))), dim3(256), 0, s, src, ld_src, dst,
-                       ld_dst, rows, cols, beta);
-  else
-    hipLaunchKernelGGL(dj_copy2d_kernel<1>, dim3(ew_blocks(rows * cols)), dim3(256), 0, s, src, ld_src, dst, ld_dst,
-                       rows, cols, beta);
-  DJ_CHECK_LAUNCH("dj_copy2d");
-  return DJ_OK;
+  return copy2d_impl<false>("dj_copy2d", src, DJ_F32, ld_src, dst, DJ_F32, ld_dst, rows, cols, beta, stream);
+}
+
+extern "C" int dj_copy2d_t(const void* src, int dt_src, long ld_src, void* dst, int dt_dst, long ld_dst, long rows, long cols,
+                           int beta, void* stream) {
+  return copy2d_impl<true>("dj_copy2d_t", src, dt_src, ld_src, dst, dt_dst, ld_dst, rows, cols, beta, stream);
 }
 
 // Up to DJ_COPY_PARTS strided 2-D copies in ONE launch (blockIdx.y = part): Concatenate of several tensors and its
@@ -1130,7 +967,7 @@ extern "C" int dj_l2norm_bwd(const float* dy, int ld_dy, const float* x, int ldx
   }
   if (dgamma_partial) {
     L2DgF f{dy, x, rnorm, ld_dy, ldx};
-    bool v4 = C % 4 == 0 && ld_dy % 4 == 0 && ldx % 4 == 0 && al16p(dy) && al16p(x) && al16p(dgamma_partial);
+    bool v4 = C % 4 == 0 && ld_dy % 4 == 0 && ldx % 4 == 0 && al16(dy) && al16(x) && al16(dgamma_partial);
     return launch_colreduce(f, rows, C, v4, dgamma_partial, s, "dj_l2norm_bwd(dgamma)");
   }
   return DJ_OK;

@@ -227,6 +227,7 @@ def conv2d_fwd_bn(desc, x, w, bias, y, bn, pro_scale=None, pro_shift=None, pro_r
                   res_shift=None, sum_out=None):
     """Forward conv + the training-mode BatchNormalization statistics / coefficients of its output in one launch."""
     import ctypes
+    assert not any16(x, w, y, res, sum_out), "conv2d_fwd_bn has no `_t` entry point: every tensor must be torch.float32"
     d = _desc_for(desc, x, y)
     assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
     check(_L().dj_conv2d_nhwc_fwd_bn(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),

@@ -4,8 +4,11 @@ wired to ResNet50Custom(archi=...) -- the committed reference config calls ResNe
 `archi` and cannot consume the [Y, CbCr] batches its own generators emit; the README's DCT experiments
 need ResNet50Custom, so that is what `--archi <dct archi>` builds here.
 
-Data: ImageNet + jpeg2dct are absent, so the generators are synthetic JPEG-DCT batches with one-hot labels (same
-emission contract as DCTGeneratorJPEG2DCT / DCTGeneratorJPEG2DCTDeconv, vgg_jpeg_keras/generators/generators.py:39-353).
+Data: ImageNet + jpeg2dct are absent, so by default the generators are synthetic JPEG-DCT batches with one-hot labels
+(same emission contract as DCTGeneratorJPEG2DCT / DCTGeneratorJPEG2DCTDeconv, vgg_jpeg_keras/generators/generators.py:39-353).
+With `DJ_TRAIN_DIR`, `DJ_VAL_DIR` and `DJ_INDEX_FILE` all set, the DCT architectures read real images through
+jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators instead; `DJ_DEVICE_PREP=1` then moves resize, crop, flip and the
+JPEG transform of those images to the GPU.
 `prepare_horovod(hvd)` reproduces the reference's data-parallel scaling rules (:121-150) with `hvd` = the RCCL adapter
 of training.py."""
 from os import environ
@@ -142,7 +145,17 @@ class TrainingConfiguration(object):
 
     def prepare_training_generators(self):
         rank = self.horovod.rank() if self.horovod is not None else 0
-        if self.archi == "resnet_rgb":
+        real = [environ.get(k) for k in ("DJ_TRAIN_DIR", "DJ_VAL_DIR", "DJ_INDEX_FILE")]
+        if all(real) and self.archi != "resnet_rgb":
+            from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (DCTGeneratorJPEG2DCT,
+                                                                                 DCTGeneratorJPEG2DCTDeconv)
+            cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
+            device_prep = environ.get("DJ_DEVICE_PREP", "0") == "1"
+            self.train_directory, self.validation_directory, self.index_file = real
+            # as the reference (:166-172), minus its photometric `transformations`, which are not ported
+            self._train_generator = cls(real[0], real[2], self._batch_size, scale=True, device_prep=device_prep)
+            self._validation_generator = cls(real[1], real[2], self._batch_size, scale=False, device_prep=device_prep)
+        elif self.archi == "resnet_rgb":
             self._train_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, seed=1000 * rank)
             self._validation_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
         else:

@@ -414,6 +414,39 @@ int dj_rgb_to_dct(const unsigned char* rgb, int batch, int height, int width, lo
                   const unsigned short* luma_table, const unsigned short* chroma_table, int normalized, float* out_y,
                   long ld_y, float* out_cb, long ld_cb, float* out_cr, long ld_cr, void* stream);
 
+/* ---- Decoded RGB images of different sizes -> one [batch][target][target][3] uint8 tensor: `im.resize(...)`, `im.crop(...)`
+ * and `im.transpose(FLIP_LEFT_RIGHT)` of the classifier generators (C/vgg_jpeg_keras/generators/generators.py:141-167,
+ * :299-325), bit for bit what Pillow's two-pass resampler leaves: per pass and sample
+ * clip8((2^21 + sum_k pixel[first + k] * tap[k]) >> 22) in 32-bit integers, a uint8 image between the passes.  The taps are a
+ * function of the two sizes and the filter alone; the caller computes them (data/image_prep.py:resample_coeffs) and passes
+ * them in an int32 pool: per axis `bounds` = one (first source index, tap count) pair per sample of the RESIZED axis and
+ * `taps` = one row of `ksize` ints per sample.  An axis whose size is unchanged (Pillow skips the pass) is passed as one
+ * tap of 2^22 per sample.  Only the target x target window at (crop_x, crop_y) of the resized image is computed: the
+ * horizontal pass runs over source rows row0 .. row0 + n_rows - 1, which must cover what the window's vertical taps read,
+ * and leaves n_rows x target pixels at scratch + scratch_offset; images' scratch regions come in batch order and do not
+ * overlap (dj_image_prep_scratch_bytes: the size when each region is rounded up to 64 bytes).
+ * src / desc_dev / pool_dev / out / scratch are DEVICE pointers; desc_host / pool_host are HOST copies of the same
+ * descriptors and pool, read during the call only: every index the kernels will form is checked against the buffer sizes
+ * before anything is launched (an error writes nothing), and the grid is sized from them -- no synchronisation, so the
+ * call stays capturable.  out: images target * out_stride_bytes apart, only the 3 * target bytes of each row are written. ---- */
+typedef struct dj_image_prep_desc {
+  long src_offset;     /* bytes from `src` to the image's first pixel */
+  long src_stride;     /* bytes between its pixel rows, >= 3 * src_w */
+  long scratch_offset; /* bytes from `scratch` to this image's horizontal-pass rows */
+  int src_h, src_w;
+  int res_h, res_w;    /* size after the resize */
+  int crop_y, crop_x;  /* origin of the window in the resized image */
+  int flip;            /* != 0: the window is mirrored left-right */
+  int h_bounds, h_taps, h_ksize; /* pool offsets (in ints) of the horizontal bounds and taps, ints per tap row */
+  int v_bounds, v_taps, v_ksize;
+  int row0, n_rows;    /* source rows the horizontal pass produces */
+} dj_image_prep_desc;
+long dj_image_prep_scratch_bytes(const dj_image_prep_desc* desc_host, int batch, int target);
+int dj_image_prep(const unsigned char* src, long src_bytes, const dj_image_prep_desc* desc_dev,
+                  const dj_image_prep_desc* desc_host, int batch, const int* pool_dev, const int* pool_host, long pool_ints,
+                  int target, unsigned char* out, long out_stride_bytes, unsigned char* scratch, long scratch_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

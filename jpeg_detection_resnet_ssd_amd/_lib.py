@@ -29,6 +29,12 @@ class ColsumPart(Structure):   # dj_colsum_part
     _fields_ = [("x", c_void_p), ("out", c_void_p), ("rows", c_long), ("C", c_int), ("ld", c_int), ("beta", c_int)]
 
 
+class ImagePrepDesc(Structure):   # dj_image_prep_desc
+    _fields_ = ([(n, c_long) for n in ("src_offset", "src_stride", "scratch_offset")]
+                + [(n, c_int) for n in ("src_h", "src_w", "res_h", "res_w", "crop_y", "crop_x", "flip", "h_bounds", "h_taps",
+                                        "h_ksize", "v_bounds", "v_taps", "v_ksize", "row0", "n_rows")])
+
+
 class ConvDesc(Structure):
     """Mirror of `dj_conv2d_desc` (include/dj_hip.h)."""
     _fields_ = [(n, c_int) for n in (
@@ -148,6 +154,9 @@ SIGNATURES = {
     "dj_global_avg_pool_bwd": (c_int, [FP, FP, c_int, c_int, c_int, c_int, c_void_p]),
     "dj_rgb_to_dct": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_int, FP, c_long, FP, c_long, FP,
                               c_long, c_void_p]),
+    "dj_image_prep_scratch_bytes": (c_long, [c_void_p, c_int, c_int]),
+    "dj_image_prep": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_long,
+                              c_void_p, c_long, c_void_p]),
 }
 
 

@@ -358,3 +358,44 @@ def rgb_to_dct(rgb_u8, tables, outs, normalized=True, stream=None):
                              int(bool(normalized)), ptr(y), _pixel_ld(y), ptr(cb), _pixel_ld(cb), ptr(cr), _pixel_ld(cr),
                              stream if stream is not None else _stream()), "dj_rgb_to_dct")
     return outs
+
+
+# ---- ragged batch of decoded images -> resized, cropped, flipped uint8 batch -------------------------------------------------
+def image_prep(src, desc_dev, desc_host, pool_dev, pool_host, target, out, scratch, stream=None):
+    """dj_image_prep: `src` 1-D uint8 CUDA tensor holding the source images, `desc_dev` the descriptors' bytes on the
+    device and `desc_host` the same descriptors as a numpy array of data/image_prep.py:DESC_DTYPE, `pool_dev` / `pool_host`
+    the int32 bounds-and-taps pool as a CUDA tensor and as a numpy array, `out` a (B, target, target, 3) uint8 CUDA tensor
+    whose rows may be strided (images dense), `scratch` a 1-D uint8 CUDA tensor of at least `image_prep_scratch_bytes`
+    laid out as the descriptors say.  `stream`: a HIP stream handle (None: the current launch stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import ImagePrepDesc
+    from .data.image_prep import DESC_DTYPE
+    assert DESC_DTYPE.itemsize == ctypes.sizeof(ImagePrepDesc), "descriptor layouts disagree"
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
+        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
+    b = desc_host.shape[0]
+    assert isinstance(pool_host, np.ndarray) and pool_host.dtype == np.int32 and pool_host.ndim == 1 \
+        and pool_host.flags.c_contiguous, "pool_host: expected a contiguous 1-D int32 array"
+    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
+            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
+    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
+    assert pool_dev.is_cuda and pool_dev.dtype == torch.int32 and pool_dev.dim() == 1 and pool_dev.is_contiguous() \
+        and pool_dev.numel() >= pool_host.size, "pool_dev: expected a contiguous 1-D int32 CUDA tensor of the pool's size"
+    target = int(target)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (b, target, target, 3), \
+        "out: expected uint8 %s, got %s %s" % ((b, target, target, 3), out.dtype, tuple(out.shape))
+    assert out.stride(3) == 1 and (target == 1 or out.stride(2) == 3), "out: pixels must be packed RGB"
+    stride = out.stride(1) if target > 1 else 3 * target
+    assert b == 1 or out.stride(0) == target * stride, "out: images must be dense"
+    check(_L().dj_image_prep(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, b, ptr(pool_dev),
+                             pool_host.ctypes.data, pool_host.size, target, ptr(out), stride, ptr(scratch), scratch.numel(),
+                             stream if stream is not None else _stream()), "dj_image_prep")
+    return out
+
+
+def image_prep_scratch_bytes(desc_host, target):
+    """Bytes of scratch dj_image_prep needs when every image's region is rounded up to 64 bytes."""
+    return check(_L().dj_image_prep_scratch_bytes(desc_host.ctypes.data, desc_host.shape[0], int(target)),
+                 "dj_image_prep_scratch_bytes")

@@ -1,0 +1,135 @@
+"""The classifier's image generators with the surface of the reference's
+(classification_part/vgg_jpeg_keras/generators/generators.py:15-353): a directory of class directories, an ImageNet-style
+index file `{"<class id>": ["<directory name>", ...]}`, and per batch `[X_y, X_cbcr]` (DCTGeneratorJPEG2DCT) or
+`[X_y, X_cb, X_cr]` (DCTGeneratorJPEG2DCTDeconv) with one-hot labels.  Per image, in the reference's order: decode and
+`convert("RGB")`, resize, `random.randint` for the crop offset (scale=True only), crop, `random.uniform` for the flip
+(flip=True only), the photometric `transformations`, JPEG emission.
+
+`device_prep=False` does all of that on the host: PIL for the pixels, then `emit_dct_inputs`.  `device_prep=True` only
+decodes and draws: the batch is a `PendingImageInputs` and resize, crop, flip and the JPEG transform run on the GPU when
+the model uploads it (data/image_prep.py, csrc/dj_imgprep.hip), bit-exact with the host path.
+
+Differences from the reference, all outside the numbers: class directories and files are listed in sorted order (the
+reference takes `os.listdir` order), inputs are float32 and labels float32 (the reference fills int32 arrays with the same
+values), and the resize filter is named explicitly (`resample`, default BICUBIC: what `im.resize(size)` has meant since
+Pillow 7)."""
+import json
+import os
+import random
+
+import numpy as np
+
+from ...data import image_prep
+from ...data.jpeg_dct import emit_dct_inputs
+from ...keras.utils import Sequence
+
+
+def prepare_imagenet(index_file, data_directory):
+    """-> ({directory name: class id}, class directory names, image paths)."""
+    with open(index_file) as f:
+        association = {value[0]: class_id for class_id, value in json.load(f).items()}
+    classes, images_path = [], []
+    for name in sorted(os.listdir(data_directory)):
+        class_directory = os.path.join(data_directory, name)
+        if os.path.isdir(class_directory):
+            classes.append(name)
+            images_path.extend(os.path.join(class_directory, image) for image in sorted(os.listdir(class_directory)))
+    return association, classes, images_path
+
+
+class DCTGeneratorJPEG2DCT(Sequence):
+    """Batches of `[X_y, X_cbcr]` ((B, T/8, T/8, 64), (B, T/16, T/16, 128)) and one-hot labels."""
+    deconv = False
+
+    def __init__(self, data_directory, index_file, batch_size=32, shuffle=True, scale=True, target_length=224, flip=True,
+                 transformations=None, device_prep=False, resample=None):
+        if device_prep and transformations is not None:
+            raise NotImplementedError(
+                "device_prep=True cannot be combined with `transformations`: the photometric callables work on host "
+                "pixels, and with device_prep the resized pixels exist on the GPU only; use device_prep=False")
+        self.association, self.classes, self.images_path = prepare_imagenet(index_file, data_directory)
+        self.batch_size = batch_size
+        self.shuffle = shuffle
+        self.number_of_data_samples = len(self.images_path)
+        self.scale = scale
+        self.target_length = target_length
+        self.flip = flip
+        self.transformations = transformations
+        self.device_prep = bool(device_prep)
+        self.resample = image_prep.resolve_resample(resample)
+        self.number_of_classes = len(self.classes)
+        self.batches_per_epoch = len(self.images_path) // self.batch_size
+        self.indexes = np.arange(len(self.images_path))
+        self._prep = image_prep.DeviceImagePrep(target_length, self.resample, deconv=self.deconv) if device_prep else None
+        self.on_epoch_end()
+
+    def __len__(self):
+        return self.batches_per_epoch
+
+    def __getitem__(self, index):
+        index = index % self.batches_per_epoch      # more steps per epoch than batches wrap around
+        return self._data_generation(self.indexes[index * self.batch_size:(index + 1) * self.batch_size])
+
+    def on_epoch_end(self):
+        if self.shuffle:
+            np.random.shuffle(self.indexes)
+
+    def _label(self, path):
+        return int(self.association[os.path.basename(os.path.dirname(path))])
+
+    def _host_pixels(self, im):
+        """Steps 2 to 5 in PIL, drawing from `random` in the reference's order."""
+        from PIL import Image
+        t = self.target_length
+        if self.scale:
+            ratio = t / min(im.size)
+            width, height = im.size
+            im = im.resize((int(round(width * ratio)), int(round(height * ratio))), self.resample)
+            offset = random.randint(0, max(im.size) - t)
+            if im.size[0] > im.size[1]:
+                im = im.crop((offset, 0, t + offset, t))
+            else:
+                im = im.crop((0, offset, t, t + offset))
+        else:
+            im = im.resize((int(t), int(t)), self.resample)
+        if self.flip and random.uniform(0, 1) > 0.5:
+            im = im.transpose(Image.FLIP_LEFT_RIGHT)
+        if self.transformations is not None:
+            pixels = np.array(im)
+            random.shuffle(self.transformations)
+            for transformation in self.transformations:
+                if random.uniform(0, 1) > 0.5:
+                    pixels = transformation(pixels)
+            im = Image.fromarray(pixels).convert("RGB")
+        return np.asarray(im)
+
+    def _draws(self, height, width):
+        """The same draws for the device path: -> (scale, offset, flip)."""
+        offset = 0
+        if self.scale:
+            offset = random.randint(0, image_prep.max_offset(height, width, self.target_length))
+        return bool(self.scale), offset, bool(self.flip and random.uniform(0, 1) > 0.5)
+
+    def _data_generation(self, indexes):
+        from PIL import Image
+        y = np.zeros((len(indexes), self.number_of_classes), dtype=np.float32)
+        images, params = [], []
+        for i, k in enumerate(indexes):
+            path = self.images_path[k]
+            with Image.open(path) as im:
+                im = im.convert("RGB")
+                if self.device_prep:
+                    pixels = np.asarray(im)
+                    images.append(pixels)
+                    params.append(self._draws(pixels.shape[0], pixels.shape[1]))
+                else:
+                    images.append(self._host_pixels(im))
+            y[i, self._label(path)] = 1
+        if self.device_prep:
+            return self._prep(images, params), y
+        return emit_dct_inputs(np.stack(images), deconv=self.deconv), y
+
+
+class DCTGeneratorJPEG2DCTDeconv(DCTGeneratorJPEG2DCT):
+    """Batches of `[X_y, X_cb, X_cr]` ((B, T/8, T/8, 64) and twice (B, T/16, T/16, 64)) and one-hot labels."""
+    deconv = True

@@ -152,8 +152,13 @@ class TrainingConfiguration(object):
             cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
             device_prep = environ.get("DJ_DEVICE_PREP", "0") == "1"
             self.train_directory, self.validation_directory, self.index_file = real
-            # as the reference (:166-172), minus its photometric `transformations`, which are not ported
-            self._train_generator = cls(real[0], real[2], self._batch_size, scale=True, device_prep=device_prep)
+            # as the reference (:166-172); its photometric `transformations` (:162) are opt-in: DJ_PHOTOMETRIC=1, on either path
+            transformations = None
+            if environ.get("DJ_PHOTOMETRIC", "0") == "1":
+                from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import brightness, contrast, lighting, saturation
+                transformations = [lighting, contrast, brightness, saturation]
+            self._train_generator = cls(real[0], real[2], self._batch_size, scale=True, device_prep=device_prep,
+                                        transformations=transformations)
             self._validation_generator = cls(real[1], real[2], self._batch_size, scale=False, device_prep=device_prep)
         elif self.archi == "resnet_rgb":
             self._train_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, seed=1000 * rank)

@@ -447,6 +447,32 @@ int dj_image_prep(const unsigned char* src, long src_bytes, const dj_image_prep_
                   int target, unsigned char* out, long out_stride_bytes, unsigned char* scratch, long scratch_bytes,
                   void* stream);
 
+/* ---- Photometric augmentation of a [batch][height][width][3] uint8 tensor IN PLACE: the `saturation`, `brightness`,
+ * `contrast` and `lighting` callables of the classifier generators (C/vgg_jpeg_keras/generators/helper.py:12-45), bit for bit
+ * what numpy computes in float64 (data/photometric.py:photometric_host states the contract: the grey value is
+ * fma(b, 0.114, fma(g, 0.587, r * 0.299)), the mean of `contrast` is numpy's pairwise sum / n, `lighting` works from exact
+ * integer moments; every operation ends in clip to [0, 255] and truncation to uint8).  Image i runs ops[i].n_ops operations
+ * in order: param[k][0] is alpha for saturation / brightness / contrast, param[k][0..2] the three normal draws times the
+ * standard deviation for lighting.  pixels / ops_dev / shift_out are DEVICE pointers, ops_host the HOST copy of the same
+ * lists, read during the call only: an unknown code, more than DJ_PHOTO_MAX_OPS operations or a parameter that is not finite
+ * is an error, and an error writes nothing.  pixels: `stride_bytes` between pixel rows, images height * stride_bytes apart,
+ * only the 3 * width bytes of each row are touched; height * width <= 2^18.  shift_out (optional, [batch][3] doubles)
+ * receives the per-channel shift the image's last lighting operation added (zeros when it has none).  One launch, no
+ * synchronisation: the call stays capturable. ---- */
+#define DJ_PHOTO_MAX_OPS 4
+#define DJ_PHOTO_SATURATION 1
+#define DJ_PHOTO_BRIGHTNESS 2
+#define DJ_PHOTO_CONTRAST 3
+#define DJ_PHOTO_LIGHTING 4
+typedef struct dj_photometric_ops {
+  int n_ops;
+  int code[DJ_PHOTO_MAX_OPS];
+  int reserved;
+  double param[DJ_PHOTO_MAX_OPS][3];
+} dj_photometric_ops;
+int dj_photometric(unsigned char* pixels, int batch, int height, int width, long stride_bytes,
+                   const dj_photometric_ops* ops_dev, const dj_photometric_ops* ops_host, double* shift_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@ class ImagePrepDesc(Structure):   # dj_image_prep_desc
                                         "h_ksize", "v_bounds", "v_taps", "v_ksize", "row0", "n_rows")])
 
 
+class PhotometricOps(Structure):   # dj_photometric_ops
+    _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
+
+
 class ConvDesc(Structure):
     """Mirror of `dj_conv2d_desc` (include/dj_hip.h)."""
     _fields_ = [(n, c_int) for n in (
@@ -157,6 +161,7 @@ SIGNATURES = {
     "dj_image_prep_scratch_bytes": (c_long, [c_void_p, c_int, c_int]),
     "dj_image_prep": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_long,
                               c_void_p, c_long, c_void_p]),
+    "dj_photometric": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

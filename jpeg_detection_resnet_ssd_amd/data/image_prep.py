@@ -215,9 +215,11 @@ def _round_up(n, a=_ALIGN):
 class BatchPlan(object):
     """Everything `dj_image_prep` needs for one ragged batch except the pixels' bytes: per-image descriptors, the shared
     int32 pool of bounds and taps (one copy per distinct (source size, resized size) pair of the batch) and the layout of
-    one staging buffer `[descriptors | pool | pixels]`, each part at a multiple of 64 bytes."""
+    one staging buffer `[descriptors | pool | photometric lists | pixels]`, each part at a multiple of 64 bytes.  `ops`
+    (optional): per image, the photometric operations [(code, parameters), ...] of data/photometric.py that
+    dj_photometric runs on the prepared pixels; without it the third part is empty."""
 
-    def __init__(self, shapes, params, target_length=224, resample=None):
+    def __init__(self, shapes, params, target_length=224, resample=None, ops=None):
         code = resolve_resample(resample)
         t = int(target_length)
         shapes = [(int(h), int(w)) for h, w in shapes]
@@ -259,13 +261,20 @@ class BatchPlan(object):
         self.src_bytes, self.scratch_bytes = src_off, scratch_off
         self.desc_offset = 0
         self.pool_offset = _round_up(self.desc.nbytes)
-        self.src_offset = self.pool_offset + _round_up(self.pool.nbytes)
+        self.ops = None
+        if ops is not None:
+            from .photometric import pack_ops
+            self.ops = pack_ops(ops, self.batch)
+        self.ops_offset = self.pool_offset + _round_up(self.pool.nbytes)
+        self.src_offset = self.ops_offset + (_round_up(self.ops.nbytes) if self.ops is not None else 0)
         self.nbytes = self.src_offset + self.src_bytes
 
     def fill(self, staging, images):
         """Write descriptors, pool and the images' pixels into `staging`, a uint8 numpy array of at least `nbytes`."""
         staging[:self.desc.nbytes] = self.desc.view(np.uint8)
         staging[self.pool_offset:self.pool_offset + self.pool.nbytes] = self.pool.view(np.uint8)
+        if self.ops is not None:
+            staging[self.ops_offset:self.ops_offset + self.ops.nbytes] = self.ops.view(np.uint8).reshape(-1)
         for d, (h, w), img in zip(self.desc, self.shapes, images):
             o = self.src_offset + int(d["src_offset"])
             staging[o:o + 3 * w * h].reshape(h, w, 3)[...] = img
@@ -282,6 +291,13 @@ class BatchPlan(object):
         return src, desc, pool.view(torch.int32)
 
 
+def _run_photometric(plan, blob_dev, pixels, shift_out=None, stream=None):
+    """dj_photometric on the prepared batch, its lists read from the device copy of the staging buffer."""
+    from .. import kernels
+    lists = blob_dev[plan.ops_offset:plan.ops_offset + plan.ops.nbytes]
+    return kernels.photometric(pixels, lists, plan.ops, shift_out=shift_out, stream=stream)
+
+
 def _check_images(images):
     images = [_check_image(im) for im in images]
     if not images:
@@ -296,13 +312,13 @@ def _run_plan(plan, blob_host, blob_dev, out, scratch, stream=None):
     return kernels.image_prep(src_d, desc_d, desc_h, pool_d, pool_h, plan.target, out, scratch, stream=stream)
 
 
-def prep_device(images, params, target_length=224, resample=None, device=None, out=None, stream=None):
+def prep_device(images, params, target_length=224, resample=None, device=None, out=None, stream=None, ops=None):
     """`prep_host` for a list of (H_i, W_i, 3) uint8 images and per-image (scale, offset, flip) on the GPU -> the
     (B, target_length, target_length, 3) uint8 CUDA batch, for callers outside `Model` (fresh buffers every call;
-    `DeviceImagePrep` keeps its own)."""
+    `DeviceImagePrep` keeps its own).  `ops`: per-image photometric operation lists, run on the prepared pixels."""
     import torch
     images = _check_images(images)
-    plan = BatchPlan([im.shape[:2] for im in images], params, target_length, resample)
+    plan = BatchPlan([im.shape[:2] for im in images], params, target_length, resample, ops=ops)
     device = torch.device(device if device is not None else "cuda")
     staging = torch.empty(plan.nbytes, dtype=torch.uint8).pin_memory()
     host = staging.numpy()
@@ -313,22 +329,30 @@ def prep_device(images, params, target_length=224, resample=None, device=None, o
         out = torch.empty((plan.batch, t, t, 3), dtype=torch.uint8, device=device)
     scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=device)
     _run_plan(plan, host, blob, out, scratch, stream=stream)
+    if plan.ops is not None:
+        _run_photometric(plan, blob, out, stream=stream)
     # the pinned buffer and the scratch go away with this frame: wait for the copy and the two passes
     (torch.cuda.current_stream(device) if stream is None else torch.cuda.ExternalStream(stream)).synchronize()
     return out
 
 
 class PendingImageInputs(object):
-    """The decoded images of one batch and their draws, to be resized, cropped, flipped and JPEG-transformed straight
-    into a model's resident input buffers at upload time: the protocol of `PendingDCTInputs` (`Model.train_on_batch /
-    predict_on_batch / predict / fit_generator` accept it where they accept the list of input arrays)."""
+    """The decoded images of one batch and their draws, to be resized, cropped, flipped, optionally augmented
+    photometrically and JPEG-transformed straight into a model's resident input buffers at upload time: the protocol of
+    `PendingDCTInputs` (`Model.train_on_batch / predict_on_batch / predict / fit_generator` accept it where they accept
+    the list of input arrays).  `ops`: None, or per image the photometric operations [(code, parameters), ...] of
+    data/photometric.py with their draws made."""
 
-    def __init__(self, prep, images, params):
+    def __init__(self, prep, images, params, ops=None):
         self.prep = prep
         self.images = _check_images(images)
         self.params = [(bool(s), int(o), bool(f)) for s, o, f in params]
+        if ops is not None:
+            from .photometric import check_ops
+            ops = check_ops(ops, len(self.images))
+        self.ops = ops
         # descriptors and taps are made where the batch is made (a generator's prefetch thread), not at upload time
-        self.plan = BatchPlan([im.shape[:2] for im in self.images], self.params, prep.target_length, prep.resample)
+        self.plan = BatchPlan([im.shape[:2] for im in self.images], self.params, prep.target_length, prep.resample, ops=ops)
 
     def __len__(self):
         return len(self.images)
@@ -342,7 +366,8 @@ class PendingImageInputs(object):
     def __getitem__(self, index):
         if not isinstance(index, slice):
             raise TypeError("PendingImageInputs can only be sliced along the batch")
-        return PendingImageInputs(self.prep, self.images[index], self.params[index])
+        return PendingImageInputs(self.prep, self.images[index], self.params[index],
+                                  None if self.ops is None else self.ops[index])
 
     @property
     def shapes(self):
@@ -351,25 +376,32 @@ class PendingImageInputs(object):
         return input_shapes(len(self.images), t, t, self.prep.deconv)
 
     def emit_into(self, buffers):
-        """One upload of `[descriptors | taps | pixels]` from pinned memory, then dj_image_prep into the emitter's resident
-        uint8 batch and dj_rgb_to_dct into `buffers` (float32 CUDA tensors of `self.shapes`), all on the current stream."""
+        """One upload of `[descriptors | taps | photometric lists | pixels]` from pinned memory, then dj_image_prep into
+        the emitter's resident uint8 batch, dj_photometric on it in place when the batch carries operation lists, and
+        dj_rgb_to_dct into `buffers` (float32 CUDA tensors of `self.shapes`), all on the current stream."""
         from .. import kernels
         buffers = list(buffers)
         if [tuple(t.shape) for t in buffers] != [tuple(s) for s in self.shapes]:
             raise ValueError("emit_into: expected buffers of shapes %s, got %s"
                              % (self.shapes, [tuple(t.shape) for t in buffers]))
         pixels = self.prep.run(self.plan, self.images, buffers[0].device)
+        if self.plan.ops is not None:
+            self.prep.photometric(self.plan, pixels)
         outs = tuple(buffers) if self.prep.deconv else (buffers[0], buffers[1][..., :64], buffers[1][..., 64:])
         kernels.rgb_to_dct(pixels, self.prep.tables, outs, normalized=True)
         return buffers
 
     def pixels(self):
-        """The (B, T, T, 3) uint8 batch computed on the host (`prep_host` per image)."""
+        """The (B, T, T, 3) uint8 batch computed on the host (`prep_host` per image, then `photometric_host`)."""
         p = self.prep
-        return np.stack([prep_host(im, p.target_length, s, o, f, p.resample) for im, (s, o, f) in zip(self.images, self.params)])
+        out = np.stack([prep_host(im, p.target_length, s, o, f, p.resample) for im, (s, o, f) in zip(self.images, self.params)])
+        if self.ops is not None:
+            from .photometric import photometric_host
+            out = photometric_host(out, self.ops)
+        return out
 
     def numpy(self):
-        """The model inputs computed on the host (`prep_host`, then `rgb_to_dct_host`, per image), float32."""
+        """The model inputs computed on the host (`pixels`, then `rgb_to_dct_host` per image), float32."""
         from .jpeg_dct import rgb_to_dct_host
         planes = [rgb_to_dct_host(img, tables=self.prep.tables) for img in self.pixels()]
         y, cb, cr = (np.stack([p[i] for p in planes]).astype(np.float32) for i in range(3))
@@ -398,8 +430,8 @@ class DeviceImagePrep(object):
         self.deconv = bool(deconv)
         self._state = {}
 
-    def __call__(self, images, params):
-        return PendingImageInputs(self, images, params)
+    def __call__(self, images, params, ops=None):
+        return PendingImageInputs(self, images, params, ops)
 
     @staticmethod
     def _grown(tensor, nbytes, make):
@@ -433,3 +465,8 @@ class DeviceImagePrep(object):
         out = st["out"][:n_out].view(plan.batch, plan.target, plan.target, 3)
         _run_plan(plan, host, st["blob"], out, st["scratch"])
         return out
+
+    def photometric(self, plan, pixels):
+        """dj_photometric on the batch `run` has just prepared for `plan`, in place, on the current stream: the
+        operation lists went up with the descriptors."""
+        return _run_photometric(plan, self._state[str(pixels.device)]["blob"], pixels)

@@ -399,3 +399,33 @@ def image_prep_scratch_bytes(desc_host, target):
     """Bytes of scratch dj_image_prep needs when every image's region is rounded up to 64 bytes."""
     return check(_L().dj_image_prep_scratch_bytes(desc_host.ctypes.data, desc_host.shape[0], int(target)),
                  "dj_image_prep_scratch_bytes")
+
+
+# ---- photometric augmentation of a uint8 batch, in place ---------------------------------------------------------------------
+def photometric(pixels, ops_dev, ops_host, shift_out=None, stream=None):
+    """dj_photometric: `pixels` a (B, H, W, 3) uint8 CUDA tensor whose rows may be strided (images dense), modified in
+    place; `ops_dev` the per-image operation lists' bytes on the device (1-D uint8) and `ops_host` the same lists as a
+    numpy array of data/photometric.py:OPS_DTYPE; `shift_out` an optional contiguous (B, 3) float64 CUDA tensor that
+    receives the lighting shifts applied.  `stream`: a HIP stream handle (None: the current launch stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import PhotometricOps
+    from .data.photometric import OPS_DTYPE
+    assert OPS_DTYPE.itemsize == ctypes.sizeof(PhotometricOps), "operation-list layouts disagree"
+    assert pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] == 3, \
+        "expected a (B, H, W, 3) uint8 CUDA tensor"
+    b, h, w, _ = pixels.shape
+    assert isinstance(ops_host, np.ndarray) and ops_host.dtype == OPS_DTYPE and ops_host.shape == (b,) \
+        and ops_host.flags.c_contiguous, "ops_host: expected a contiguous array of one OPS_DTYPE entry per image"
+    assert ops_dev.is_cuda and ops_dev.dtype == torch.uint8 and ops_dev.dim() == 1 and ops_dev.is_contiguous() \
+        and ops_dev.numel() >= ops_host.nbytes and ops_dev.data_ptr() % 8 == 0, \
+        "ops_dev: expected a contiguous, 8-byte aligned 1-D uint8 CUDA tensor of the lists' size"
+    assert pixels.stride(3) == 1 and (w == 1 or pixels.stride(2) == 3), "pixels must be packed RGB"
+    stride = pixels.stride(1) if h > 1 else (pixels.stride(0) if b > 1 else 3 * w)      # one row per image: its pitch is the image pitch
+    assert stride >= 3 * w and (b == 1 or pixels.stride(0) == h * stride), "images must be dense"
+    if shift_out is not None:
+        assert shift_out.is_cuda and shift_out.dtype == torch.float64 and tuple(shift_out.shape) == (b, 3) \
+            and shift_out.is_contiguous(), "shift_out: expected a contiguous (B, 3) float64 CUDA tensor"
+    check(_L().dj_photometric(ptr(pixels), b, h, w, stride, ptr(ops_dev), ops_host.ctypes.data, ptr(shift_out),
+                              stream if stream is not None else _stream()), "dj_photometric")
+    return pixels

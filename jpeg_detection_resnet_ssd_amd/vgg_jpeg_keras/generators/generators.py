@@ -6,8 +6,11 @@ index file `{"<class id>": ["<directory name>", ...]}`, and per batch `[X_y, X_c
 (flip=True only), the photometric `transformations`, JPEG emission.
 
 `device_prep=False` does all of that on the host: PIL for the pixels, then `emit_dct_inputs`.  `device_prep=True` only
-decodes and draws: the batch is a `PendingImageInputs` and resize, crop, flip and the JPEG transform run on the GPU when
-the model uploads it (data/image_prep.py, csrc/dj_imgprep.hip), bit-exact with the host path.
+decodes and draws: the batch is a `PendingImageInputs` and resize, crop, flip, the photometric operations and the JPEG
+transform run on the GPU when the model uploads it (data/image_prep.py, csrc/dj_imgprep.hip, csrc/dj_photometric.hip),
+bit-exact with the host path.  On the device path `transformations` may hold only `saturation`, `brightness`, `contrast`
+and `lighting` of helper.py (recognised by identity): their draws from `np.random` are made here, in the host path's
+order, and travel with the batch.
 
 Differences from the reference, all outside the numbers: class directories and files are listed in sorted order (the
 reference takes `os.listdir` order), inputs are float32 and labels float32 (the reference fills int32 arrays with the same
@@ -22,6 +25,7 @@ import numpy as np
 from ...data import image_prep
 from ...data.jpeg_dct import emit_dct_inputs
 from ...keras.utils import Sequence
+from . import helper
 
 
 def prepare_imagenet(index_file, data_directory):
@@ -43,10 +47,15 @@ class DCTGeneratorJPEG2DCT(Sequence):
 
     def __init__(self, data_directory, index_file, batch_size=32, shuffle=True, scale=True, target_length=224, flip=True,
                  transformations=None, device_prep=False, resample=None):
-        if device_prep and transformations is not None:
+        if device_prep and transformations is not None and \
+                not all(helper.photometric_code(t) is not None for t in transformations):
             raise NotImplementedError(
-                "device_prep=True cannot be combined with `transformations`: the photometric callables work on host "
-                "pixels, and with device_prep the resized pixels exist on the GPU only; use device_prep=False")
+                "device_prep=True can be combined with `transformations` made of saturation, brightness, contrast and "
+                "lighting of vgg_jpeg_keras.generators only: any other callable works on host pixels, and with "
+                "device_prep the resized pixels exist on the GPU only; use device_prep=False")
+        if device_prep and transformations is not None and len(transformations) > 4:
+            raise NotImplementedError("device_prep=True runs at most 4 `transformations` per image, got %d"
+                                      % len(transformations))
         self.association, self.classes, self.images_path = prepare_imagenet(index_file, data_directory)
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -104,16 +113,22 @@ class DCTGeneratorJPEG2DCT(Sequence):
         return np.asarray(im)
 
     def _draws(self, height, width):
-        """The same draws for the device path: -> (scale, offset, flip)."""
+        """The same draws for the device path, in the same order: -> ((scale, offset, flip), photometric operations or
+        None).  A transformation that is taken makes its own draw from `np.random`, as the callable would."""
         offset = 0
         if self.scale:
             offset = random.randint(0, image_prep.max_offset(height, width, self.target_length))
-        return bool(self.scale), offset, bool(self.flip and random.uniform(0, 1) > 0.5)
+        flip = bool(self.flip and random.uniform(0, 1) > 0.5)
+        ops = None
+        if self.transformations is not None:
+            random.shuffle(self.transformations)
+            ops = [helper.draw_parameters(t) for t in self.transformations if random.uniform(0, 1) > 0.5]
+        return (bool(self.scale), offset, flip), ops
 
     def _data_generation(self, indexes):
         from PIL import Image
         y = np.zeros((len(indexes), self.number_of_classes), dtype=np.float32)
-        images, params = [], []
+        images, params, ops = [], [], []
         for i, k in enumerate(indexes):
             path = self.images_path[k]
             with Image.open(path) as im:
@@ -121,12 +136,14 @@ class DCTGeneratorJPEG2DCT(Sequence):
                 if self.device_prep:
                     pixels = np.asarray(im)
                     images.append(pixels)
-                    params.append(self._draws(pixels.shape[0], pixels.shape[1]))
+                    draws, image_ops = self._draws(pixels.shape[0], pixels.shape[1])
+                    params.append(draws)
+                    ops.append(image_ops)
                 else:
                     images.append(self._host_pixels(im))
             y[i, self._label(path)] = 1
         if self.device_prep:
-            return self._prep(images, params), y
+            return self._prep(images, params, ops if self.transformations is not None else None), y
         return emit_dct_inputs(np.stack(images), deconv=self.deconv), y
 
 

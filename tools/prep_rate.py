@@ -7,6 +7,9 @@ tensors at 224x224, host path vs device path:
   (c) the two kernels alone, by device events, and their bytes moved over that time
   (d) Model.fit_generator img/s of the batch-64 deconv classifier fed by a generator that emits the same decoded
       batches through (a) or through (b)
+  (e) the photometric stage (saturation, brightness, contrast, lighting, each drawn with probability 1/2 per image in a
+      shuffled order, as the generators do): the device path with dj_photometric between the two kernels, the kernel
+      alone by events, and the four numpy callables on the 64 prepared images on 16 threads
 
     python tools/prep_rate.py [--reps 20] [--fit-steps 40] [--no-fit]
 
@@ -26,7 +29,7 @@ import numpy as np
 import torch
 
 from jpeg_detection_resnet_ssd_amd import kernels
-from jpeg_detection_resnet_ssd_amd.data import image_prep, jpeg_dct
+from jpeg_detection_resnet_ssd_amd.data import image_prep, jpeg_dct, photometric
 
 HBM_MEASURED_GBS = 6290.0     # float4 copy on MI355X (tools/input_rate.py)
 T = 224
@@ -45,12 +48,17 @@ def median_ms(fn, reps, warmup=3):
     return statistics.median(out), min(out), max(out)
 
 
-def event_ms(fn, reps):
+def event_ms(fn, reps, setup=None):
+    """`setup` runs before every repetition, ahead of the first event: its time is not counted."""
     for _ in range(5):
+        if setup is not None:
+            setup()
         fn()
     times = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if setup is not None:
+            setup()
         e0.record()
         fn()
         e1.record()
@@ -71,6 +79,20 @@ def make_batch(rng, n):
         images.append(np.clip(img + rng.normal(0, 15, img.shape), 0, 255).astype(np.uint8))
         params.append((True, int(rng.integers(0, image_prep.max_offset(h, w, T) + 1)), bool(rng.random() > 0.5)))
     return images, params
+
+
+def make_ops(rng, n):
+    """Per image: the four operations in a shuffled order, each taken with probability 1/2, parameters as the callables
+    draw them."""
+    ops = []
+    for _ in range(n):
+        lst = []
+        for code in rng.permutation([photometric.LIGHTING, photometric.CONTRAST, photometric.BRIGHTNESS, photometric.SATURATION]):
+            if rng.random() > 0.5:
+                lst.append((int(code), tuple(rng.standard_normal(3) * 0.5) if code == photometric.LIGHTING
+                            else (0.5 + rng.random(),)))
+        ops.append(lst)
+    return ops
 
 
 def pil_prep(img, scale, offset, flip):
@@ -149,6 +171,34 @@ def main():
     res["image_prep_ms"], res["image_prep_bytes"], res["image_prep_GBs"] = prep_ms, prep_bytes, prep_bytes / prep_ms[0] / 1e6
     res["rgb_to_dct_ms"], res["rgb_to_dct_bytes"], res["rgb_to_dct_GBs"] = dct_ms, dct_bytes, dct_bytes / dct_ms[0] / 1e6
     res["kernels_share_of_measured_hbm"] = (prep_bytes + dct_bytes) / (prep_ms[0] + dct_ms[0]) / 1e6 / HBM_MEASURED_GBS
+    # (e) the photometric stage
+    ops = make_ops(rng, B)
+    res["photometric_ops_per_image"] = float(np.mean([len(o) for o in ops]))
+    res["device_photometric_ms"] = median_ms(lambda: prep(images, params, ops).emit_into(bufs), args.reps)
+    with_ops = prep(images, params, ops)
+    res["device_photometric_emit_only_ms"] = median_ms(lambda: with_ops.emit_into(bufs), args.reps)
+    ops_host = with_ops.plan.ops
+    ops_dev = torch.from_numpy(ops_host.view(np.uint8).reshape(-1).copy()).to(dev)
+    image_prep._run_plan(plan, host, blob, pixels, scratch)
+    prepared_dev = pixels.clone()
+
+    def restore():          # the kernel works in place: every repetition starts from the prepared batch again
+        pixels.copy_(prepared_dev)
+    res["photometric_ms"] = event_ms(lambda: kernels.photometric(pixels, ops_dev, ops_host), reps, setup=restore)
+    all_four = photometric.pack_ops([[(c, (0.1, 0.2, -0.1) if c == photometric.LIGHTING else (0.9,)) for c in (4, 3, 2, 1)]] * B)
+    all_dev = torch.from_numpy(all_four.view(np.uint8).reshape(-1).copy()).to(dev)
+    res["photometric_all_four_ms"] = event_ms(lambda: kernels.photometric(pixels, all_dev, all_four), reps, setup=restore)
+    from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import brightness, contrast, lighting, saturation
+    by_code = {photometric.SATURATION: saturation, photometric.BRIGHTNESS: brightness, photometric.CONTRAST: contrast,
+               photometric.LIGHTING: lighting}
+    prepared = prepared_dev.cpu().numpy()
+
+    def callables(a):
+        img, lst = a
+        for code, _ in lst:
+            img = by_code[code](img)
+        return img
+    res["host_callables_ms"] = median_ms(lambda: list(pool.map(callables, zip(prepared, ops))), max(5, args.reps // 2))
     res["mean_taps"] = [float(np.mean([plan.pool[int(x["h_bounds"]) + 1:int(x["h_bounds"]) + 2 * T:2].mean() for x in d])),
                         float(np.mean([plan.pool[int(x["v_bounds"]) + 1:int(x["v_bounds"]) + 2 * T:2].mean() for x in d]))]
     res["h_grid_fill"] = float(rows.mean() / rows.max())      # share of the horizontal pass's blocks that have work

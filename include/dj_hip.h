@@ -473,6 +473,39 @@ typedef struct dj_photometric_ops {
 int dj_photometric(unsigned char* pixels, int batch, int height, int width, long stride_bytes,
                    const dj_photometric_ops* ops_dev, const dj_photometric_ops* ops_host, double* shift_out, void* stream);
 
+/* ---- A window of each decoded RGB image on a constant background, optionally mirrored, resized -> one
+ * [batch][out_h][out_w][3] uint8 tensor: the expand, crop, flip and resize stages of the SSD augmentation chain composed
+ * (data/ssd_augment.py), bit for bit what data/patch_resize.py:patch_resize_host states in numpy: the window is a canvas of
+ * `background` with the image under it pasted in, mirrored left-right when `flip` is set, then resized as Pillow's
+ * Image.resize does, with dj_image_prep's arithmetic (two passes, clip8((2^21 + sum_k pixel[first + k] * tap[k]) >> 22), a
+ * uint8 image between them).  Bounds and taps come from the caller in an int32 pool as for dj_image_prep, here per axis for
+ * window size -> output size: `bounds` = one (first window sample, tap count) pair per OUTPUT sample, `taps` = one row of
+ * `ksize` ints per output sample; an unchanged axis, and Pillow's NEAREST, travel as one tap of 2^22 per sample.
+ * Only the rectangle of the image that the window covers needs to be staged: src_h x src_w is that rectangle (0 x 0 when
+ * the window misses the image: every sample is background) and the window origin is relative to it, so it may be negative
+ * and the window may extend past either far edge.  The horizontal pass leaves win_h x out_w pixels at scratch +
+ * scratch_offset; images' scratch regions come in batch order and do not overlap (dj_patch_resize_scratch_bytes: the size
+ * when each region is rounded up to 64 bytes).  Pointers, the host copies, the checks before anything is launched (an error
+ * writes nothing) and capturability as for dj_image_prep.  out: images out_h * out_stride_bytes apart, only the 3 * out_w
+ * bytes of each row are written. ---- */
+typedef struct dj_patch_resize_desc {
+  long src_offset;     /* bytes from `src` to the staged rectangle's first pixel */
+  long src_stride;     /* bytes between its pixel rows, >= 3 * src_w */
+  long scratch_offset; /* bytes from `scratch` to this image's horizontal-pass rows */
+  int src_h, src_w;    /* size of the staged rectangle */
+  int win_y0, win_x0;  /* origin of the window relative to the staged rectangle, any sign */
+  int win_h, win_w;
+  int flip;            /* != 0: the window is mirrored left-right before the resize */
+  int background;      /* r | g << 8 | b << 16 */
+  int h_bounds, h_taps, h_ksize; /* pool offsets (in ints) of the bounds and taps for win_w -> out_w, ints per tap row */
+  int v_bounds, v_taps, v_ksize; /* the same for win_h -> out_h */
+} dj_patch_resize_desc;
+long dj_patch_resize_scratch_bytes(const dj_patch_resize_desc* desc_host, int batch, int out_w);
+int dj_patch_resize(const unsigned char* src, long src_bytes, const dj_patch_resize_desc* desc_dev,
+                    const dj_patch_resize_desc* desc_host, int batch, const int* pool_dev, const int* pool_host,
+                    long pool_ints, int out_h, int out_w, unsigned char* out, long out_stride_bytes, unsigned char* scratch,
+                    long scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,12 @@ class ImagePrepDesc(Structure):   # dj_image_prep_desc
                                         "h_ksize", "v_bounds", "v_taps", "v_ksize", "row0", "n_rows")])
 
 
+class PatchResizeDesc(Structure):   # dj_patch_resize_desc
+    _fields_ = ([(n, c_long) for n in ("src_offset", "src_stride", "scratch_offset")]
+                + [(n, c_int) for n in ("src_h", "src_w", "win_y0", "win_x0", "win_h", "win_w", "flip", "background", "h_bounds",
+                                        "h_taps", "h_ksize", "v_bounds", "v_taps", "v_ksize")])
+
+
 class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
@@ -162,6 +168,9 @@ SIGNATURES = {
     "dj_image_prep": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_long,
                               c_void_p, c_long, c_void_p]),
     "dj_photometric": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dj_patch_resize_scratch_bytes": (c_long, [c_void_p, c_int, c_int]),
+    "dj_patch_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
+                                c_long, c_void_p, c_long, c_void_p]),
 }
 
 

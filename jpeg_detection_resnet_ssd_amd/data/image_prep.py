@@ -48,8 +48,18 @@ def _box(x):
     return np.where((x > -0.5) & (x <= 0.5), 1.0, 0.0)
 
 
+def _lanczos(x):
+    # Pillow's truncated sinc, a = 3: sinc(x) * sinc(x / 3) on -3 <= x < 3, with sinc(x) = sin(pi x) / (pi x)
+    def sinc(v):
+        v = v * math.pi
+        return np.where(v == 0.0, 1.0, np.sin(v) / np.where(v == 0.0, 1.0, v))
+    return np.where((x >= -3.0) & (x < 3.0), sinc(x) * sinc(x / 3), 0.0)
+
+
 _FILTERS = {BICUBIC: (_bicubic, 2.0), BILINEAR: (_bilinear, 1.0), BOX: (_box, 0.5)}     # code -> (filter, support)
 SUPPORTED = tuple(sorted(_FILTERS))
+# restated for data/patch_resize.py only: `resolve_resample`, and with it every entry point of this module, keeps refusing it
+_MORE_FILTERS = {LANCZOS: (_lanczos, 3.0)}
 
 
 def resolve_resample(resample):
@@ -69,7 +79,7 @@ def resolve_resample(resample):
 
 @functools.lru_cache(maxsize=4096)
 def _coeffs(in_size, out_size, code):
-    filt, support = _FILTERS[code]
+    filt, support = _FILTERS[code] if code in _FILTERS else _MORE_FILTERS[code]
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
     support = support * filterscale

@@ -429,3 +429,45 @@ def photometric(pixels, ops_dev, ops_host, shift_out=None, stream=None):
     check(_L().dj_photometric(ptr(pixels), b, h, w, stride, ptr(ops_dev), ops_host.ctypes.data, ptr(shift_out),
                               stream if stream is not None else _stream()), "dj_photometric")
     return pixels
+
+
+# ---- ragged batch of decoded images -> a window of each on a background, mirrored, resized -----------------------------------
+def patch_resize(src, desc_dev, desc_host, pool_dev, pool_host, out, scratch, stream=None):
+    """dj_patch_resize: `src` 1-D uint8 CUDA tensor holding the staged rectangles, `desc_dev` the descriptors' bytes on the
+    device and `desc_host` the same descriptors as a numpy array of data/patch_resize.py:DESC_DTYPE, `pool_dev` /
+    `pool_host` the int32 bounds-and-taps pool as a CUDA tensor and as a numpy array, `out` a (B, out_h, out_w, 3) uint8
+    CUDA tensor whose rows may be strided (images dense), `scratch` a 1-D uint8 CUDA tensor of at least
+    `patch_resize_scratch_bytes` laid out as the descriptors say.  `stream`: a HIP stream handle (None: the current launch
+    stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import PatchResizeDesc
+    from .data.patch_resize import DESC_DTYPE
+    assert DESC_DTYPE.itemsize == ctypes.sizeof(PatchResizeDesc), "descriptor layouts disagree"
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
+        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
+    b = desc_host.shape[0]
+    assert isinstance(pool_host, np.ndarray) and pool_host.dtype == np.int32 and pool_host.ndim == 1 \
+        and pool_host.flags.c_contiguous, "pool_host: expected a contiguous 1-D int32 array"
+    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
+            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
+    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
+    assert pool_dev.is_cuda and pool_dev.dtype == torch.int32 and pool_dev.dim() == 1 and pool_dev.is_contiguous() \
+        and pool_dev.numel() >= pool_host.size, "pool_dev: expected a contiguous 1-D int32 CUDA tensor of the pool's size"
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 4 and out.shape[0] == b and out.shape[3] == 3, \
+        "out: expected a (%d, out_h, out_w, 3) uint8 CUDA tensor, got %s %s" % (b, out.dtype, tuple(out.shape))
+    out_h, out_w = int(out.shape[1]), int(out.shape[2])
+    assert out.stride(3) == 1 and (out_w == 1 or out.stride(2) == 3), "out: pixels must be packed RGB"
+    stride = out.stride(1) if out_h > 1 else (out.stride(0) if b > 1 else 3 * out_w)      # one row per image: its pitch is the image pitch
+    assert stride >= 3 * out_w and (b == 1 or out.stride(0) == out_h * stride), "out: images must be dense"
+    check(_L().dj_patch_resize(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, b, ptr(pool_dev),
+                               pool_host.ctypes.data, pool_host.size, out_h, out_w, ptr(out), stride, ptr(scratch),
+                               scratch.numel(), stream if stream is not None else _stream()), "dj_patch_resize")
+    return out
+
+
+def patch_resize_scratch_bytes(desc_host, out_w):
+    """Bytes of scratch dj_patch_resize needs when every image's region is rounded up to 64 bytes."""
+    return check(_L().dj_patch_resize_scratch_bytes(desc_host.ctypes.data, desc_host.shape[0], int(out_w)),
+                 "dj_patch_resize_scratch_bytes")

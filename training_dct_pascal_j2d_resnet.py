@@ -5,8 +5,11 @@ ones), same environment variables, same model / optimizer / loss / encoder / cal
     python3 training_dct_pascal_j2d_resnet.py -vd 0 --crop --p07p12 --reg --resnet --archi ssd_custom
 
 Differences, all forced by what is absent offline: the Pascal-VOC DataGeneratorDCT (PIL / cv2 / jpeg2dct) is
-replaced by a synthetic JPEG-DCT generator with the same emission contract unless `--generator module:factory` names
-a user-supplied one; checkpoints are .npz name->array archives (h5py is not installed); `--weights` goes straight to
+replaced by a synthetic JPEG-DCT generator with the same emission contract unless `DATASET_PATH` points at a Pascal-VOC
+tree in the reference's layout (VOC2007/ and, with --p07p12, VOC2012/, each with JPEGImages, Annotations and
+ImageSets/Main: then data/voc_generator.py reads it, augmented by data/ssd_augment.py as --crop / --no_crop select, on
+the host or, with `DJ_DEVICE_PREP=1`, planned on the host and run on the GPU) or `--generator module:factory` names a
+user-supplied one; checkpoints are .npz name->array archives (h5py is not installed); `--weights` goes straight to
 `load_weights(by_name=True)` (the reference's preceding `load_model` only prints a summary).
 Multi-GPU (not in the reference: "no multi-GPU support for this part") = one process per GPU:
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 training_dct_pascal_j2d_resnet.py ...
@@ -111,6 +114,16 @@ if world > 1:
 if args.generator:
     mod, fn = args.generator.split(":")
     train_dataset, val_dataset = getattr(importlib.import_module(mod), fn)(args)
+elif os.environ.get("DATASET_PATH"):
+    from jpeg_detection_resnet_ssd_amd.data.voc_generator import DataGeneratorDCT
+    years = ["VOC2007", "VOC2012"] if args.p07p12 else ["VOC2007"]
+    dirs = [os.path.join(os.environ["DATASET_PATH"], y) for y in years]
+    train_dataset, val_dataset = DataGeneratorDCT(), DataGeneratorDCT()
+    for dataset, image_set, exclude_difficult in ((train_dataset, "train.txt", False), (val_dataset, "val.txt", True)):
+        dataset.parse_xml(images_dirs=[os.path.join(d, "JPEGImages") for d in dirs],
+                          image_set_filenames=[os.path.join(d, "ImageSets", "Main", image_set) for d in dirs],
+                          annotations_dirs=[os.path.join(d, "Annotations") for d in dirs], include_classes="all",
+                          exclude_truncated=False, exclude_difficult=exclude_difficult, ret=False)
 else:
     from jpeg_detection_resnet_ssd_amd.data.generators import SyntheticDataGeneratorDCT
     train_dataset = SyntheticDataGeneratorDCT(n_images=args.synthetic_images, seed=1234 + 100000 * rank)
@@ -136,11 +149,25 @@ if os.environ.get("DJ_DEVICE_DCT", "0") == "1":
     # tests/test_rgb_dct_gpu.py) runs on the GPU at upload time
     from jpeg_detection_resnet_ssd_amd.data.jpeg_dct import DeviceDCTEmitter
     emit_kwargs["dct_emitter"] = DeviceDCTEmitter(quality=75, deconv=deconv)
-train_generator = train_dataset.generate(batch_size=batch_size, shuffle=True, transformations=[],
+train_transformations, val_transformations = [], []
+if os.environ.get("DATASET_PATH") and not args.generator:
+    # the reference's chains without their photometric stage (cv2 colour conversions; data/ssd_augment.py takes a host
+    # callable for that slot), its plain Resize for validation
+    from jpeg_detection_resnet_ssd_amd.data.ssd_augment import Resize, SSDDataAugmentation, SSDDataAugmentationNoCrop
+    chain = SSDDataAugmentation if args.crop else SSDDataAugmentationNoCrop
+    train_transformations = [chain(img_height=img_height, img_width=img_width)]
+    val_transformations = [Resize(height=img_height, width=img_width)]
+    emit_kwargs.pop("dct_emitter", None)      # the VOC generator's device switch is DJ_DEVICE_PREP
+    if os.environ.get("DJ_DEVICE_PREP", "0") == "1":
+        # opt-in: the generator decodes and plans, window + mirror + resize + JPEG transform run on the GPU at upload time
+        # (tests/test_ssd_augment_gpu.py)
+        from jpeg_detection_resnet_ssd_amd.data.patch_resize import DevicePatchResize
+        emit_kwargs["device_prep"] = DevicePatchResize(img_height, img_width, quality=75, deconv=deconv)
+train_generator = train_dataset.generate(batch_size=batch_size, shuffle=True, transformations=train_transformations,
                                          label_encoder=label_encoder,
                                          returns={"processed_images", "encoded_labels"},
                                          keep_images_without_gt=False, deconv=deconv, **emit_kwargs)
-val_generator = val_dataset.generate(batch_size=batch_size, shuffle=False, transformations=[],
+val_generator = val_dataset.generate(batch_size=batch_size, shuffle=False, transformations=val_transformations,
                                      label_encoder=label_encoder, returns={"processed_images", "encoded_labels"},
                                      keep_images_without_gt=False, deconv=deconv, **emit_kwargs)
 train_dataset_size = train_dataset.get_dataset_size()

@@ -506,6 +506,40 @@ int dj_patch_resize(const unsigned char* src, long src_bytes, const dj_patch_res
                     long pool_ints, int out_h, int out_w, unsigned char* out, long out_stride_bytes, unsigned char* scratch,
                     long scratch_bytes, void* stream);
 
+/* ---- The photometric stage of the SSD augmentation chain (`SSDPhotometricDistortions`) IN PLACE on the staged rectangles of
+ * a ragged batch, before dj_patch_resize reads them: byte for byte what data/ssd_photometric.py:ssd_photometric_host states
+ * in numpy.  Per pixel, with everything between bytes in float32, every operation rounding on its own and bytes made by
+ * rounding half to even:
+ *   sequence 1: brightness, contrast, ->u8, RGB->HSV, saturation, hue, ->u8, HSV->RGB, channel order
+ *   sequence 2: brightness, ->u8, RGB->HSV, saturation, hue, ->u8, HSV->RGB, contrast, ->u8, channel order
+ * brightness clip(x + delta, 0, 255), contrast clip(127.5 + factor * (x - 127.5), 0, 255), saturation clip(S * factor, 0, 255),
+ * hue remainder(H + delta, 180) with the divisor's sign; the colour conversions are OpenCV's 8-bit ones (H in 0..180) as that
+ * module restates them, and they run whatever `flags` selects.  Output channel k is channel order[k] of the result.
+ * The rectangles are those of the dj_patch_resize descriptors (src_offset, src_stride, src_h, src_w; nothing else of a
+ * descriptor is read): only the 3 * src_w bytes of each staged row are touched, and an image with a 0 x 0 rectangle costs
+ * nothing.  src / desc_dev / params_dev are DEVICE pointers, desc_host / params_host the HOST copies, read during the call
+ * only and checked before anything is launched: a sequence other than 1 or 2, unknown flags, a parameter that is not finite
+ * (those of operations that are off included: they travel as zero), an order that is no permutation of (0, 1, 2), a
+ * rectangle that leaves `src_bytes` or holds 2^31 pixels or more is an error, and an error writes nothing.  One launch, no
+ * synchronisation: the call stays capturable. ---- */
+#define DJ_SSD_PHOTO_BRIGHTNESS 1
+#define DJ_SSD_PHOTO_CONTRAST 2
+#define DJ_SSD_PHOTO_SATURATION 4
+#define DJ_SSD_PHOTO_HUE 8
+typedef struct dj_ssd_photo_params {
+  int sequence;        /* 1 or 2 */
+  int flags;           /* DJ_SSD_PHOTO_* of the operations that were drawn */
+  float brightness;    /* delta */
+  float contrast;      /* factor */
+  float saturation;    /* factor */
+  float hue;           /* delta */
+  int order[3];
+  int reserved;
+} dj_ssd_photo_params;
+int dj_ssd_photometric(unsigned char* src, long src_bytes, const dj_patch_resize_desc* desc_dev,
+                       const dj_patch_resize_desc* desc_host, const dj_ssd_photo_params* params_dev,
+                       const dj_ssd_photo_params* params_host, int batch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

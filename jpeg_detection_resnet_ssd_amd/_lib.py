@@ -45,6 +45,11 @@ class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
 
+class SsdPhotoParams(Structure):   # dj_ssd_photo_params
+    _fields_ = [("sequence", c_int), ("flags", c_int), ("brightness", c_float), ("contrast", c_float), ("saturation", c_float),
+                ("hue", c_float), ("order", c_int * 3), ("reserved", c_int)]
+
+
 class ConvDesc(Structure):
     """Mirror of `dj_conv2d_desc` (include/dj_hip.h)."""
     _fields_ = [(n, c_int) for n in (
@@ -171,6 +176,7 @@ SIGNATURES = {
     "dj_patch_resize_scratch_bytes": (c_long, [c_void_p, c_int, c_int]),
     "dj_patch_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
                                 c_long, c_void_p, c_long, c_void_p]),
+    "dj_ssd_photometric": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 

@@ -140,9 +140,12 @@ class PatchPlan(object):
     """Everything `dj_patch_resize` needs for one ragged batch except the pixels' bytes: per-image descriptors, the shared
     int32 pool of bounds and taps (one copy per distinct (window size, output size, filter) triple of the batch) and the
     layout of one staging buffer `[descriptors | pool | pixels]`, each part at a multiple of 64 bytes.  Only the
-    rectangle of each image that its window covers is staged: the descriptor's window is relative to that rectangle."""
+    rectangle of each image that its window covers is staged: the descriptor's window is relative to that rectangle.
+    `photometric` (optional): per image, the `PhotoParams` of data/ssd_photometric.py that dj_ssd_photometric applies to
+    the staged rectangles before the resize; the records then travel as a fourth part behind the pixels.  Without them
+    there is no such part and the layout is the three-part one."""
 
-    def __init__(self, shapes, geometries, out_height, out_width):
+    def __init__(self, shapes, geometries, out_height, out_width, photometric=None):
         shapes = [(int(h), int(w)) for h, w in shapes]
         geometries = [check_geometry(g) for g in geometries]
         if len(shapes) != len(geometries) or not shapes:
@@ -189,11 +192,22 @@ class PatchPlan(object):
         self.pool_offset = _round_up(self.desc.nbytes)
         self.src_offset = self.pool_offset + _round_up(self.pool.nbytes)
         self.nbytes = self.src_offset + self.src_bytes
+        self.photo = self.photo_offset = None
+        if photometric is not None:
+            from .ssd_photometric import pack_params
+            self.photo = pack_params(photometric)
+            if len(self.photo) != self.batch:
+                raise ValueError("expected one photometric record per image: %d records for %d images"
+                                 % (len(self.photo), self.batch))
+            self.photo_offset = _round_up(self.nbytes)
+            self.nbytes = self.photo_offset + self.photo.nbytes
 
     def fill(self, staging, images):
-        """Write descriptors, pool and the staged rectangles' pixels into `staging`, a uint8 numpy array of at least
-        `nbytes`."""
+        """Write descriptors, pool, the staged rectangles' pixels and the photometric records, if any, into `staging`, a
+        uint8 numpy array of at least `nbytes`."""
         staging[:self.desc.nbytes] = self.desc.view(np.uint8)
+        if self.photo is not None:
+            staging[self.photo_offset:self.photo_offset + self.photo.nbytes] = self.photo.view(np.uint8)
         staging[self.pool_offset:self.pool_offset + self.pool.nbytes] = self.pool.view(np.uint8)
         for d, (ya, yb, xa, xb), img in zip(self.desc, self.rects, images):
             if yb > ya:
@@ -211,21 +225,35 @@ class PatchPlan(object):
         import torch
         return src, desc, pool.view(torch.int32)
 
+    def photo_view(self, blob):
+        """The photometric records of a staging buffer or of its device copy (a PARAMS_DTYPE array, or bytes for a torch
+        tensor); None for a plan without them."""
+        if self.photo is None:
+            return None
+        part = blob[self.photo_offset:self.photo_offset + self.photo.nbytes]
+        if isinstance(blob, np.ndarray):
+            from .ssd_photometric import PARAMS_DTYPE
+            return part.view(PARAMS_DTYPE)
+        return part
+
 
 def _run_plan(plan, blob_host, blob_dev, out, scratch, stream=None):
     from .. import kernels
     src_h, desc_h, pool_h = plan.views(blob_host)
     src_d, desc_d, pool_d = plan.views(blob_dev)
+    if plan.photo is not None:         # in place on the staged rectangles, before the resize reads them
+        kernels.ssd_photometric(src_d, desc_d, desc_h, plan.photo_view(blob_dev), plan.photo_view(blob_host), stream=stream)
     return kernels.patch_resize(src_d, desc_d, desc_h, pool_d, pool_h, out, scratch, stream=stream)
 
 
-def patch_resize_device(images, geometries, out_height, out_width, device=None, out=None, stream=None):
+def patch_resize_device(images, geometries, out_height, out_width, device=None, out=None, stream=None, photometric=None):
     """`patch_resize_host` for a list of (H_i, W_i, 3) uint8 images and one geometry each on the GPU -> the
     (B, out_height, out_width, 3) uint8 CUDA batch, for callers outside `Model` (fresh buffers every call;
-    `DevicePatchResize` keeps its own)."""
+    `DevicePatchResize` keeps its own).  `photometric`: one `PhotoParams` per image, applied before the window is cut
+    (`ssd_photometric_host`)."""
     import torch
     images = ip._check_images(images)
-    plan = PatchPlan([im.shape[:2] for im in images], geometries, out_height, out_width)
+    plan = PatchPlan([im.shape[:2] for im in images], geometries, out_height, out_width, photometric)
     device = torch.device(device if device is not None else "cuda")
     staging = torch.empty(plan.nbytes, dtype=torch.uint8).pin_memory()
     host = staging.numpy()
@@ -244,14 +272,20 @@ class PendingPatchInputs(object):
     """The decoded images of one batch and their geometries, to be windowed, mirrored, resized and JPEG-transformed
     straight into a model's resident input buffers at upload time: the protocol of `PendingImageInputs`
     (`Model.train_on_batch / predict_on_batch / predict / fit_generator` accept it where they accept the list of input
-    arrays)."""
+    arrays).  `photometric`: one `PhotoParams` of data/ssd_photometric.py per image, or None; the stage runs on the
+    decoded image, before its window is cut (dj_ssd_photometric on the GPU, `ssd_photometric_host` in the host twins)."""
 
-    def __init__(self, prep, images, geometries):
+    def __init__(self, prep, images, geometries, photometric=None):
         self.prep = prep
         self.images = ip._check_images(images)
         self.geometries = [check_geometry(g) for g in geometries]
+        self.photometric = None
+        if photometric is not None:
+            from .ssd_photometric import check_params
+            self.photometric = [check_params(p) for p in photometric]
         # descriptors and taps are made where the batch is made (a generator's prefetch thread), not at upload time
-        self.plan = PatchPlan([im.shape[:2] for im in self.images], self.geometries, prep.out_height, prep.out_width)
+        self.plan = PatchPlan([im.shape[:2] for im in self.images], self.geometries, prep.out_height, prep.out_width,
+                              self.photometric)
 
     def __len__(self):
         return len(self.images)
@@ -264,7 +298,8 @@ class PendingPatchInputs(object):
     def __getitem__(self, index):
         if not isinstance(index, slice):
             raise TypeError("PendingPatchInputs can only be sliced along the batch")
-        return PendingPatchInputs(self.prep, self.images[index], self.geometries[index])
+        return PendingPatchInputs(self.prep, self.images[index], self.geometries[index],
+                                  self.photometric[index] if self.photometric is not None else None)
 
     @property
     def shapes(self):
@@ -272,9 +307,9 @@ class PendingPatchInputs(object):
         return input_shapes(len(self.images), self.prep.out_height, self.prep.out_width, self.prep.deconv)
 
     def emit_into(self, buffers):
-        """One upload of `[descriptors | taps | pixels]` from pinned memory, then dj_patch_resize into the emitter's
-        resident uint8 batch and dj_rgb_to_dct into `buffers` (float32 CUDA tensors of `self.shapes`), all on the
-        current stream."""
+        """One upload of `[descriptors | taps | pixels | photometric records]` from pinned memory, then
+        dj_ssd_photometric on the staged pixels when there are records, dj_patch_resize into the emitter's resident uint8
+        batch and dj_rgb_to_dct into `buffers` (float32 CUDA tensors of `self.shapes`), all on the current stream."""
         from .. import kernels
         buffers = list(buffers)
         if [tuple(t.shape) for t in buffers] != [tuple(s) for s in self.shapes]:
@@ -286,9 +321,14 @@ class PendingPatchInputs(object):
         return buffers
 
     def pixels(self):
-        """The (B, out_height, out_width, 3) uint8 batch computed on the host (`patch_resize_host` per image)."""
+        """The (B, out_height, out_width, 3) uint8 batch computed on the host (`ssd_photometric_host` where there are
+        records, then `patch_resize_host`, per image)."""
         p = self.prep
-        return np.stack([patch_resize_host(im, g, p.out_height, p.out_width) for im, g in zip(self.images, self.geometries)])
+        images = self.images
+        if self.photometric is not None:
+            from .ssd_photometric import ssd_photometric_host
+            images = [ssd_photometric_host(im, rec) for im, rec in zip(images, self.photometric)]
+        return np.stack([patch_resize_host(im, g, p.out_height, p.out_width) for im, g in zip(images, self.geometries)])
 
     def numpy(self):
         """The model inputs computed on the host (`pixels`, then `rgb_to_dct_host` per image), float32."""
@@ -302,7 +342,8 @@ class DevicePatchResize(object):
     """Stands where the reference's SSD generator runs the geometric stages of its augmentation chain in numpy and cv2
     and then saves each image as a JPEG and reads it back: the generator thread only decodes and plans
     (`SSDDataAugmentation.plan`), the covered part of each image goes up once and both steps run on the GPU when the model
-    uploads the batch.  `quality` / `tables` / `deconv` as for `DeviceDCTEmitter`.
+    uploads the batch -- after the chain's photometric stage, when the plan drew one (`photometric`).  `quality` / `tables`
+    / `deconv` as for `DeviceDCTEmitter`.
 
     Buffers are kept per emitter and device and grown on demand, as in `DeviceImagePrep`: two pinned staging buffers used
     in turn, each refilled only after the upload that last read it has finished, the device copy of the staging buffer,
@@ -318,12 +359,13 @@ class DevicePatchResize(object):
         self.deconv = bool(deconv)
         self._state = {}
 
-    def __call__(self, images, geometries):
-        return PendingPatchInputs(self, images, geometries)
+    def __call__(self, images, geometries, photometric=None):
+        return PendingPatchInputs(self, images, geometries, photometric)
 
     def run(self, plan, images, device):
-        """Stage, upload and launch dj_patch_resize for `plan` on the current stream -> the resident
-        (B, out_height, out_width, 3) uint8 batch (valid until the next call on this device)."""
+        """Stage, upload and launch dj_ssd_photometric (for a plan with records) and dj_patch_resize for `plan` on the
+        current stream -> the resident (B, out_height, out_width, 3) uint8 batch (valid until the next call on this
+        device)."""
         import torch
         grown = ip.DeviceImagePrep._grown
         device = torch.device(device)

@@ -1,4 +1,4 @@
-"""The geometric part of the SSD300 training augmentation: `SSDDataAugmentation` and what it is made of, restated from the
+"""The SSD300 training augmentation: `SSDDataAugmentation` and the geometric transforms it is made of, restated from the
 reference's localisation_part/data_generator (data_augmentation_chain_original_ssd.py, ..._no_crop.py,
 object_detection_2d_patch_sampling_ops.py, object_detection_2d_image_boxes_validation_utils.py,
 object_detection_2d_geometric_ops.py) with its constructor arguments, its defaults and its order of `np.random` draws, so
@@ -10,12 +10,18 @@ same label arithmetic and touches no pixel: expand, crop and flip compose into o
 constant background, which `data/patch_resize.py` then resamples on the host (`patch_resize_host`) or on the GPU
 (`DevicePatchResize`).
 
+The photometric stage, `SSDPhotometricDistortions`, lives in data/ssd_photometric.py and is re-exported here.  Given to a
+chain's `photometric_distortions` slot it runs first, as in the reference: on pixels in the chain's call, and as a drawn
+`PhotoParams` record in `plan(..., return_photometric=True)`, which `ssd_photometric_host` or the GPU (dj_ssd_photometric,
+before the window is cut) then applies.  The chains' default leaves the slot empty.
+
 Two departures from the reference, both on the pixel side only:
   * the resize is Pillow's, not OpenCV's (no OpenCV here to pin it to): the five interpolation codes the chain draws from
     map to NEAREST, BILINEAR, BICUBIC, BOX and LANCZOS (`CV2_TO_PILLOW`).  Pillow antialiases when it shrinks, OpenCV's
     linear and cubic modes do not;
-  * `SSDPhotometricDistortions` (cv2 colour conversions) is not restated: the chain takes an optional host callable
-    `(image, labels) -> (image, labels)` for that slot and skips the stage without one."""
+  * the colour conversions of the photometric stage are the in-tree restatement of OpenCV's 8-bit formulas
+    (data/ssd_photometric.py), not calls into a cv2 build.
+The slot also takes any other host callable `(image, labels) -> (image, labels)`; such a callable cannot be planned."""
 import inspect
 
 import numpy as np
@@ -23,6 +29,7 @@ import numpy as np
 from ..bounding_box_utils.bounding_box_utils import iou
 from . import patch_resize as _pr
 from .patch_resize import patch_resize_host, resize_host, window_host      # noqa: F401  (the pixel contract, re-exported)
+from .ssd_photometric import SSDPhotometricDistortions, ssd_photometric_host      # noqa: F401  (the photometric stage)
 
 # OpenCV's interpolation codes, which the reference's constructors take, and the Pillow filter each one runs as here
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
@@ -645,7 +652,8 @@ class SSDExpand(_Plannable):
 class _SSDChain(object):
     def _build(self, img_height, img_width, background, labels_format, photometric_distortions):
         if photometric_distortions is not None and not callable(photometric_distortions):
-            raise ValueError("`photometric_distortions` must be None or a callable (image, labels) -> (image, labels)")
+            raise ValueError("`photometric_distortions` must be None, an `SSDPhotometricDistortions` or a callable "
+                             "(image, labels) -> (image, labels)")
         self.labels_format = labels_format
         self.photometric_distortions = photometric_distortions
         self.expand = SSDExpand(background=background, labels_format=self.labels_format)
@@ -681,19 +689,34 @@ class _SSDChain(object):
         head = [self.photometric_distortions] if self.photometric_distortions is not None else []
         return self._run(image, labels, return_inverter, head + self.sequence)
 
-    def plan(self, height, width, labels, return_inverter=False):
+    @property
+    def plans_photometric(self):
+        """Whether the photometric slot holds a stage whose draws `plan(..., return_photometric=True)` can make."""
+        return hasattr(self.photometric_distortions, 'draw')
+
+    def plan(self, height, width, labels, return_inverter=False, return_photometric=False):
         """The draws and the label arithmetic of the geometric stages for an image of (height, width), no pixel touched
         -> (geometry, labels[, inverters]) with geometry = (win_y0, win_x0, win_h, win_w, flip, filter, background) of
-        data/patch_resize.py, or None when the chain gives up.  The photometric callable is not part of it: run it on
-        the decoded image first."""
+        data/patch_resize.py, or None when the chain gives up.  With `return_photometric` the draws of the photometric
+        stage are made first, as the chain's call makes them, and their `PhotoParams` record comes back as an extra last
+        element (None for an empty slot; a plain callable in the slot cannot be planned and raises): apply it to the
+        decoded image (`ssd_photometric_host`, dj_ssd_photometric) before the window is cut.  Without the argument the
+        photometric slot is not part of the plan and no draw is made for it."""
+        record = None
+        if return_photometric and self.photometric_distortions is not None:
+            if not self.plans_photometric:
+                raise ValueError("plan: the photometric callable %r has no `draw` and cannot be planned"
+                                 % (self.photometric_distortions,))
+            record = self.photometric_distortions.draw()
         out = self._run(Geometry(height, width), labels, return_inverter, self.sequence)
         if out[0] is None:
             return None
-        return (out[0].astuple(),) + tuple(out[1:])
+        out = (out[0].astuple(),) + tuple(out[1:])
+        return out + (record,) if return_photometric else out
 
 
 class SSDDataAugmentation(_SSDChain):
-    """The augmentation of the original SSD training: [photometric callable,] expand, random crop, random flip, resize
+    """The augmentation of the original SSD training: [photometric stage,] expand, random crop, random flip, resize
     with a randomly drawn interpolation."""
 
     def __init__(self, img_height=300, img_width=300, background=(123, 117, 104), labels_format=_LABELS_FORMAT,
@@ -703,7 +726,7 @@ class SSDDataAugmentation(_SSDChain):
 
 
 class SSDDataAugmentationNoCrop(_SSDChain):
-    """The reference's `..._no_crop` variant: [photometric callable,] random flip and resize only (expand and crop are built,
+    """The reference's `..._no_crop` variant: [photometric stage,] random flip and resize only (expand and crop are built,
     as there, and not run)."""
 
     def __init__(self, img_height=300, img_width=300, background=(123, 117, 104), labels_format=_LABELS_FORMAT,

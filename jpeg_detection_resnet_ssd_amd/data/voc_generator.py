@@ -6,10 +6,13 @@ installed here (xml.etree for the annotations, PIL for decoding, the in-tree rea
 `emit_dct_inputs` makes the model inputs.  With `device_prep=DevicePatchResize(...)` every transformation is PLANNED
 (`transform.plan`: same draws, same boxes, no pixel touched), the plans of one image compose into one geometry, the
 images are only decoded, and the first item of the batch is a `PendingPatchInputs`: window, mirror, resize and the JPEG
-transform run on the GPU when the model uploads the batch.  Both paths leave bit-identical inputs.
+transform run on the GPU when the model uploads the batch.  A chain with a drawable photometric stage
+(`SSDDataAugmentation(..., photometric_distortions=SSDPhotometricDistortions())`) is asked for that stage's draws too
+(`plan(..., return_photometric=True)`), and the records go to `device_prep(images, geometries, photometric=records)`: the
+stage then runs on the GPU on the staged pixels, before the window is cut.  Both paths leave bit-identical inputs.
 
 Differences from the reference: images are decoded with `convert("RGB")` (its `ConvertTo3Channels` lives in the
-photometric stage, which is a caller-supplied callable here); the dataset is reshuffled with `np.random.permutation`
+photometric stage, which sees three channels here); the dataset is reshuffled with `np.random.permutation`
 when a pass ends (sklearn is not used); HDF5 datasets and `parse_csv` / `parse_json` are not restated."""
 import inspect
 import os
@@ -173,6 +176,7 @@ class DataGeneratorDCT(object):
 
             remove, batch_inverse_transforms = [], []
             batch_geometry = [None] * len(batch_X)
+            batch_photometric = [None] * len(batch_X)
             for i in range(len(batch_X)):
                 if batch_y is not None:
                     batch_y[i] = np.array(batch_y[i])
@@ -196,7 +200,12 @@ class DataGeneratorDCT(object):
                             kwargs['return_inverter'] = True
                         else:
                             inverter = False
+                        photometric = bool(getattr(transform, 'plans_photometric', False))
+                        if photometric:
+                            kwargs['return_photometric'] = True
                         out = planner(height, width, labels, **kwargs)
+                        if photometric and out is not None:
+                            batch_photometric[i], out = out[-1], out[:-1]
                         out = (None,) if out is None else (out if labels is not None or inverter else (out,))
                     else:
                         args = (batch_X[i],) + ((labels,) if labels is not None else ())
@@ -230,8 +239,8 @@ class DataGeneratorDCT(object):
                             if batch_y[i].size == 0 and not keep_images_without_gt:
                                 remove.append(i)
             for j in sorted(remove, reverse=True):
-                for items in (batch_X, batch_geometry, batch_filenames, batch_inverse_transforms, batch_y, batch_image_ids,
-                              batch_eval_neutral, batch_original_images, batch_original_labels):
+                for items in (batch_X, batch_geometry, batch_photometric, batch_filenames, batch_inverse_transforms, batch_y,
+                              batch_image_ids, batch_eval_neutral, batch_original_images, batch_original_labels):
                     if items is not None:
                         items.pop(j)
             if not batch_X:
@@ -248,7 +257,10 @@ class DataGeneratorDCT(object):
                     if _resize_target(transform) not in (None, size):
                         raise ValueError("device_prep resizes to %s but %r was built for %s"
                                          % (size, transform, _resize_target(transform)))
-                processed = device_prep(batch_X, geometries)
+                if any(rec is not None for rec in batch_photometric):
+                    processed = device_prep(batch_X, geometries, photometric=batch_photometric)
+                else:
+                    processed = device_prep(batch_X, geometries)
             else:
                 shapes = {im.shape for im in batch_X}
                 if len(shapes) != 1:

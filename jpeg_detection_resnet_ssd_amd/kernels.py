@@ -471,3 +471,32 @@ def patch_resize_scratch_bytes(desc_host, out_w):
     """Bytes of scratch dj_patch_resize needs when every image's region is rounded up to 64 bytes."""
     return check(_L().dj_patch_resize_scratch_bytes(desc_host.ctypes.data, desc_host.shape[0], int(out_w)),
                  "dj_patch_resize_scratch_bytes")
+
+
+# ---- the photometric stage of the SSD augmentation chain, in place on the staged rectangles ----------------------------------
+def ssd_photometric(src, desc_dev, desc_host, params_dev, params_host, stream=None):
+    """dj_ssd_photometric: `src` the 1-D uint8 CUDA tensor holding the staged rectangles that dj_patch_resize will read,
+    modified in place; `desc_dev` / `desc_host` the descriptors as for `patch_resize`; `params_dev` the per-image records'
+    bytes on the device (1-D uint8) and `params_host` the same records as a numpy array of
+    data/ssd_photometric.py:PARAMS_DTYPE.  `stream`: a HIP stream handle (None: the current launch stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import PatchResizeDesc, SsdPhotoParams
+    from .data.patch_resize import DESC_DTYPE
+    from .data.ssd_photometric import PARAMS_DTYPE
+    assert DESC_DTYPE.itemsize == ctypes.sizeof(PatchResizeDesc), "descriptor layouts disagree"
+    assert PARAMS_DTYPE.itemsize == ctypes.sizeof(SsdPhotoParams), "parameter-record layouts disagree"
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
+        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
+    b = desc_host.shape[0]
+    assert isinstance(params_host, np.ndarray) and params_host.dtype == PARAMS_DTYPE and params_host.shape == (b,) \
+        and params_host.flags.c_contiguous, "params_host: expected a contiguous array of one PARAMS_DTYPE record per image"
+    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (params_dev, "params_dev")):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
+            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
+    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
+    assert params_dev.numel() >= params_host.nbytes and params_dev.data_ptr() % 4 == 0, "params_dev: too small or misaligned"
+    check(_L().dj_ssd_photometric(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, ptr(params_dev),
+                                  params_host.ctypes.data, b, stream if stream is not None else _stream()),
+          "dj_ssd_photometric")
+    return src

@@ -7,6 +7,11 @@ path, with the geometries drawn by `SSDDataAugmentation.plan` under a fixed seed
   (b) device: `plan` per image, DevicePatchResize: one upload of descriptors + taps + the covered rectangles from pinned
               memory, dj_patch_resize, dj_rgb_to_dct
   (c) the two kernels alone, by device events, and their bytes moved over that time; the pinned upload of their input
+  (d) the photometric stage (`SSDPhotometricDistortions`, drawn per image under the same seed, before the geometry, as the
+      chain draws it): the host statement `ssd_photometric_host` on 16 threads (`photometric_host_ms`), the device path
+      with the stage (`device_photometric_ms` beside `device_ms`, `device_photometric_emit_only_ms` beside
+      `device_emit_only_ms`), and dj_ssd_photometric alone by events on the staged rectangles (`ssd_photometric_ms`, bytes
+      read and written once each) beside `patch_resize_ms` on the same batch
 
     python tools/ssd_input_rate.py [--reps 20]
 
@@ -152,6 +157,41 @@ def main():
     res["patch_resize_GBs"] = patch_bytes / patch_ms[0] / 1e6
     res["rgb_to_dct_ms"], res["rgb_to_dct_bytes"], res["rgb_to_dct_GBs"] = dct_ms, dct_bytes, dct_bytes / dct_ms[0] / 1e6
     res["kernels_share_of_measured_hbm"] = (patch_bytes + dct_bytes) / (patch_ms[0] + dct_ms[0]) / 1e6 / HBM_MEASURED_GBS
+    # (d) the photometric stage
+    staged_chain = ssd_augment.SSDDataAugmentation(OUT, OUT, photometric_distortions=ssd_augment.SSDPhotometricDistortions())
+
+    def plan_all_photometric():
+        np.random.seed(1)
+        out = [staged_chain.plan(im.shape[0], im.shape[1], y, return_photometric=True) for im, y in zip(images, labels)]
+        return [o[0] for o in out], [o[-1] for o in out]
+    geometries_p, records = plan_all_photometric()
+    res["photometric_ops_per_image"] = float(np.mean([sum(v is not None for v in r[1:5]) for r in records]))
+    res["photometric_host_ms"] = median_ms(
+        lambda: list(pool.map(lambda a: ssd_augment.ssd_photometric_host(*a), zip(images, records))), max(5, args.reps // 2))
+
+    def device_photometric():
+        g, r = plan_all_photometric()
+        prep(images, g, photometric=r).emit_into(bufs)
+    res["device_photometric_ms"] = median_ms(device_photometric, args.reps)
+    pending_p = prep(images, geometries_p, photometric=records)
+    res["device_photometric_emit_only_ms"] = median_ms(lambda: pending_p.emit_into(bufs), args.reps)
+    res["device_photometric_equals_host"] = all(torch.equal(a.cpu(), torch.from_numpy(b)) for a, b in zip(bufs, pending_p.numpy()))
+    plan_p = pending_p.plan
+    staging_p = torch.empty(plan_p.nbytes, dtype=torch.uint8).pin_memory()
+    plan_p.fill(staging_p.numpy(), images)
+    host_p = staging_p.numpy()
+    blob_p = staging_p.to(dev)
+    src_d, desc_d, _ = plan_p.views(blob_p)
+    _, desc_h, _ = plan_p.views(host_p)
+    # in place, over and over on the same bytes: the work per pixel does not depend on their values
+    photo_ms = event_ms(lambda: kernels.ssd_photometric(src_d, desc_d, desc_h, plan_p.photo_view(blob_p), plan_p.photo_view(host_p)),
+                        reps)
+    dp = plan_p.desc
+    photo_bytes = int(2 * (dp["src_h"].astype(np.int64) * dp["src_w"] * 3).sum())
+    res["ssd_photometric_ms"], res["ssd_photometric_bytes"] = photo_ms, photo_bytes
+    res["ssd_photometric_GBs"] = photo_bytes / photo_ms[0] / 1e6
+    scratch_p = torch.empty(plan_p.scratch_bytes, dtype=torch.uint8, device=dev)
+    res["photometric_plus_patch_resize_ms"] = event_ms(lambda: patch_resize._run_plan(plan_p, host_p, blob_p, pixels, scratch_p), reps)
     res["mean_taps"] = [float(np.mean([plan.pool[int(x["h_bounds"]) + 1:int(x["h_bounds"]) + 2 * OUT:2].mean() for x in d])),
                         float(np.mean([plan.pool[int(x["v_bounds"]) + 1:int(x["v_bounds"]) + 2 * OUT:2].mean() for x in d]))]
     res["h_grid_fill"] = float(rows.mean() / rows.max())      # share of the horizontal pass's blocks that have work

@@ -151,11 +151,14 @@ if os.environ.get("DJ_DEVICE_DCT", "0") == "1":
     emit_kwargs["dct_emitter"] = DeviceDCTEmitter(quality=75, deconv=deconv)
 train_transformations, val_transformations = [], []
 if os.environ.get("DATASET_PATH") and not args.generator:
-    # the reference's chains without their photometric stage (cv2 colour conversions; data/ssd_augment.py takes a host
-    # callable for that slot), its plain Resize for validation
-    from jpeg_detection_resnet_ssd_amd.data.ssd_augment import Resize, SSDDataAugmentation, SSDDataAugmentationNoCrop
+    # the reference's chains, its plain Resize for validation.  Their photometric stage (brightness, contrast, saturation
+    # and hue jitter, data/ssd_photometric.py) is opt-in: DJ_PHOTOMETRIC=1, on the host path and, with DJ_DEVICE_PREP=1, on
+    # the GPU (tests/test_ssd_photometric_gpu.py); validation is never distorted
+    from jpeg_detection_resnet_ssd_amd.data.ssd_augment import (Resize, SSDDataAugmentation, SSDDataAugmentationNoCrop,
+                                                                SSDPhotometricDistortions)
     chain = SSDDataAugmentation if args.crop else SSDDataAugmentationNoCrop
-    train_transformations = [chain(img_height=img_height, img_width=img_width)]
+    photometric = SSDPhotometricDistortions() if os.environ.get("DJ_PHOTOMETRIC", "0") == "1" else None
+    train_transformations = [chain(img_height=img_height, img_width=img_width, photometric_distortions=photometric)]
     val_transformations = [Resize(height=img_height, width=img_width)]
     emit_kwargs.pop("dct_emitter", None)      # the VOC generator's device switch is DJ_DEVICE_PREP
     if os.environ.get("DJ_DEVICE_PREP", "0") == "1":

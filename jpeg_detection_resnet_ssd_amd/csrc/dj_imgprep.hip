@@ -13,18 +13,11 @@
 // blockIdx.y is the image, blockIdx.x runs over the largest image's samples and the blocks past a smaller image leave at
 // once.  One thread owns one pixel (three accumulators); neighbouring lanes read neighbouring source bytes and the taps
 // are shared by all rows (horizontal pass) or by the whole wave (vertical pass), so both passes live in L1 / L2.
-#include "../../include/dj_hip.h"
-#include "dj_common.h"
+#include "dj_resample.h"
 
 #define DJ_IMGPREP_THREADS 256
-#define DJ_IMGPREP_BITS 22                // Pillow's PRECISION_BITS for 8-bit images
-#define DJ_IMGPREP_MAX_SIDE 65536
+#define DJ_IMGPREP_MAX_SIDE DJ_RESAMPLE_MAX_SIDE
 #define DJ_IMGPREP_MAX_TARGET 8192
-#define DJ_IMGPREP_SCRATCH_ALIGN 64
-
-__device__ __forceinline__ unsigned char imgprep_clip8(int s) {
-  return (unsigned char)min(max(s >> DJ_IMGPREP_BITS, 0), 255);
-}
 
 __global__ __launch_bounds__(DJ_IMGPREP_THREADS) void dj_imgprep_h_kernel(const unsigned char* __restrict__ src,
                                                                           const dj_image_prep_desc* __restrict__ desc,
@@ -39,17 +32,9 @@ __global__ __launch_bounds__(DJ_IMGPREP_THREADS) void dj_imgprep_h_kernel(const 
   const int first = bounds[0], n = bounds[1];
   const int* taps = pool + d.h_taps + (long)col * d.h_ksize;
   const unsigned char* p = src + d.src_offset + (long)(d.row0 + r) * d.src_stride + 3L * first;
-  int s0 = 1 << (DJ_IMGPREP_BITS - 1), s1 = s0, s2 = s0;
-  for (int t = 0; t < n; ++t) {
-    const int c = taps[t];
-    s0 += p[3 * t] * c;
-    s1 += p[3 * t + 1] * c;
-    s2 += p[3 * t + 2] * c;
-  }
-  unsigned char* o = scratch + d.scratch_offset + ((long)r * T + j) * 3;
-  o[0] = imgprep_clip8(s0);
-  o[1] = imgprep_clip8(s1);
-  o[2] = imgprep_clip8(s2);
+  int s0, s1, s2;
+  dj_accumulate_taps(p, 3, taps, n, s0, s1, s2);
+  dj_store_clip8(scratch + d.scratch_offset + ((long)r * T + j) * 3, s0, s1, s2);
 }
 
 __global__ __launch_bounds__(DJ_IMGPREP_THREADS) void dj_imgprep_v_kernel(const unsigned char* __restrict__ scratch,
@@ -62,28 +47,10 @@ __global__ __launch_bounds__(DJ_IMGPREP_THREADS) void dj_imgprep_v_kernel(const 
   if (idx >= T * T) return;
   const int y = idx / T, j = idx - y * T;
   const int row = d.crop_y + y;
-  const int* bounds = pool + d.v_bounds + 2 * row;
-  const int first = bounds[0] - d.row0, n = bounds[1];
-  const int* taps = pool + d.v_taps + (long)row * d.v_ksize;
-  const long pitch = 3L * T;
-  const unsigned char* p = scratch + d.scratch_offset + (long)first * pitch + 3L * j;
-  int s0 = 1 << (DJ_IMGPREP_BITS - 1), s1 = s0, s2 = s0;
-  for (int t = 0; t < n; ++t) {
-    const int c = taps[t];
-    s0 += p[t * pitch] * c;
-    s1 += p[t * pitch + 1] * c;
-    s2 += p[t * pitch + 2] * c;
-  }
   const int jj = d.flip ? T - 1 - j : j;      // FLIP_LEFT_RIGHT on the store
-  unsigned char* o = out + ((long)blockIdx.y * T + y) * out_stride + 3L * jj;
-  o[0] = imgprep_clip8(s0);
-  o[1] = imgprep_clip8(s1);
-  o[2] = imgprep_clip8(s2);
-}
-
-static long imgprep_scratch_of(const dj_image_prep_desc* d, int target) {
-  const long bytes = 3L * target * d->n_rows;
-  return (bytes + DJ_IMGPREP_SCRATCH_ALIGN - 1) / DJ_IMGPREP_SCRATCH_ALIGN * DJ_IMGPREP_SCRATCH_ALIGN;
+  dj_vertical_sample(pool + d.v_bounds + 2 * row, pool + d.v_taps + (long)row * d.v_ksize,
+                     scratch + d.scratch_offset + 3L * j, d.row0, 3L * T,
+                     out + ((long)blockIdx.y * T + y) * out_stride + 3L * jj);
 }
 
 extern "C" long dj_image_prep_scratch_bytes(const dj_image_prep_desc* desc_host, int batch, int target) {
@@ -97,20 +64,9 @@ extern "C" long dj_image_prep_scratch_bytes(const dj_image_prep_desc* desc_host,
       dj_set_error("image_prep_scratch_bytes: image %d: n_rows %d outside 1..%d", i, desc_host[i].n_rows, DJ_IMGPREP_MAX_SIDE);
       return DJ_ERR_ARG;
     }
-    total += imgprep_scratch_of(desc_host + i, target);
+    total += dj_scratch_region_bytes(3L * target * desc_host[i].n_rows);
   }
   return total;
-}
-
-// bounds + taps of one axis: `count` pairs at `b_off`, `count` rows of `ksize` taps at `k_off`, all inside the pool
-static int imgprep_check_axis(const char* axis, int i, long b_off, long k_off, int ksize, int count, long pool_ints) {
-  DJ_CHECK_ARG(ksize >= 1 && ksize <= DJ_IMGPREP_MAX_SIDE, "image_prep: image %d: %s tap row length %d outside 1..%d", i, axis,
-               ksize, DJ_IMGPREP_MAX_SIDE);
-  DJ_CHECK_ARG(b_off >= 0 && b_off + 2L * count <= pool_ints, "image_prep: image %d: %s bounds [%ld, %ld) leave the pool of %ld",
-               i, axis, b_off, b_off + 2L * count, pool_ints);
-  DJ_CHECK_ARG(k_off >= 0 && k_off + (long)ksize * count <= pool_ints, "image_prep: image %d: %s taps [%ld, %ld) leave the pool of %ld",
-               i, axis, k_off, k_off + (long)ksize * count, pool_ints);
-  return DJ_OK;
 }
 
 extern "C" int dj_image_prep(const unsigned char* src, long src_bytes, const dj_image_prep_desc* desc_dev,
@@ -149,8 +105,8 @@ extern "C" int dj_image_prep(const unsigned char* src, long src_bytes, const dj_
     DJ_CHECK_ARG(d->row0 >= 0 && d->n_rows >= 1 && (long)d->row0 + d->n_rows <= d->src_h,
                  "image_prep: image %d: source rows [%d, %d + %d) leave the image of %d rows", i, d->row0, d->row0, d->n_rows,
                  d->src_h);
-    if (imgprep_check_axis("horizontal", i, d->h_bounds, d->h_taps, d->h_ksize, d->res_w, pool_ints) != DJ_OK ||
-        imgprep_check_axis("vertical", i, d->v_bounds, d->v_taps, d->v_ksize, d->res_h, pool_ints) != DJ_OK)
+    if (dj_check_axis("image_prep", "horizontal", i, d->h_bounds, d->h_taps, d->h_ksize, d->res_w, pool_ints) != DJ_OK ||
+        dj_check_axis("image_prep", "vertical", i, d->v_bounds, d->v_taps, d->v_ksize, d->res_h, pool_ints) != DJ_OK)
       return DJ_ERR_ARG;
     // every read of the two passes stays inside the source rows / the scratch rows
     for (int j = 0; j < T; ++j) {
@@ -163,10 +119,8 @@ extern "C" int dj_image_prep(const unsigned char* src, long src_bytes, const dj_
                    "image_prep: image %d: row %d reads source rows [%d, %d + %d) outside [%d, %d + %d) (tap row length %d)", i,
                    d->crop_y + j, bv[0], bv[0], bv[1], d->row0, d->row0, d->n_rows, d->v_ksize);
     }
-    DJ_CHECK_ARG(d->scratch_offset >= scratch_end && d->scratch_offset + 3L * T * d->n_rows <= scratch_bytes,
-                 "image_prep: image %d: scratch [%ld, + %ld) overlaps image %d's or leaves the buffer of %ld bytes", i,
-                 d->scratch_offset, 3L * T * d->n_rows, i - 1, scratch_bytes);
-    scratch_end = d->scratch_offset + 3L * T * d->n_rows;
+    if (dj_check_scratch_region("image_prep", i, d->scratch_offset, 3L * T * d->n_rows, &scratch_end, scratch_bytes) != DJ_OK)
+      return DJ_ERR_ARG;
     if (d->n_rows > max_rows) max_rows = d->n_rows;
   }
   const dim3 block(DJ_IMGPREP_THREADS);

@@ -14,18 +14,12 @@
 // vertical pass reads those and writes the output.  One launch per pass covers the ragged batch: blockIdx.y is the image,
 // blockIdx.x runs over the tallest window's samples and the blocks past a smaller one leave at once.  One thread owns
 // one pixel (three accumulators), as in dj_imgprep.hip, whose passes are bound by the number of byte loads, not by bytes.
-#include "../../include/dj_hip.h"
-#include "dj_common.h"
+#include "dj_resample.h"
 
 #define DJ_PATCH_THREADS 256
-#define DJ_PATCH_BITS 22                  // Pillow's PRECISION_BITS for 8-bit images
-#define DJ_PATCH_MAX_SIDE 65536           // of the staged rectangle and of the window
+#define DJ_PATCH_MAX_SIDE DJ_RESAMPLE_MAX_SIDE      // of the staged rectangle and of the window
 #define DJ_PATCH_MAX_OUT 8192
 #define DJ_PATCH_MAX_ORIGIN (1 << 24)     // |window origin|: keeps every int the kernels form far from overflow
-
-__device__ __forceinline__ unsigned char patch_clip8(int s) {
-  return (unsigned char)min(max(s >> DJ_PATCH_BITS, 0), 255);
-}
 
 __global__ __launch_bounds__(DJ_PATCH_THREADS) void dj_patch_h_kernel(const unsigned char* __restrict__ src,
                                                                       const dj_patch_resize_desc* __restrict__ desc,
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(DJ_PATCH_THREADS) void dj_patch_h_kernel(const unsi
   const int* taps = pool + d.h_taps + (long)j * d.h_ksize;
   const int bg0 = d.background & 255, bg1 = (d.background >> 8) & 255, bg2 = (d.background >> 16) & 255;
   const int row = d.win_y0 + r;
-  int s0 = 1 << (DJ_PATCH_BITS - 1), s1 = s0, s2 = s0;
+  int s0 = 1 << (DJ_RESAMPLE_BITS - 1), s1 = s0, s2 = s0;
   if (row >= 0 && row < d.src_h) {
     const unsigned char* line = src + d.src_offset + (long)row * d.src_stride;
     // image column of window column `first`, and the step from one tap to the next
@@ -66,10 +60,7 @@ __global__ __launch_bounds__(DJ_PATCH_THREADS) void dj_patch_h_kernel(const unsi
     s1 += bg1 * sum;
     s2 += bg2 * sum;
   }
-  unsigned char* o = scratch + d.scratch_offset + ((long)r * out_w + j) * 3;
-  o[0] = patch_clip8(s0);
-  o[1] = patch_clip8(s1);
-  o[2] = patch_clip8(s2);
+  dj_store_clip8(scratch + d.scratch_offset + ((long)r * out_w + j) * 3, s0, s1, s2);
 }
 
 __global__ __launch_bounds__(DJ_PATCH_THREADS) void dj_patch_v_kernel(const unsigned char* __restrict__ scratch,
@@ -81,42 +72,8 @@ __global__ __launch_bounds__(DJ_PATCH_THREADS) void dj_patch_v_kernel(const unsi
   const int idx = blockIdx.x * DJ_PATCH_THREADS + threadIdx.x;
   if (idx >= out_h * out_w) return;
   const int y = idx / out_w, j = idx - y * out_w;
-  const int* bounds = pool + d.v_bounds + 2 * y;
-  const int first = bounds[0], n = bounds[1];
-  const int* taps = pool + d.v_taps + (long)y * d.v_ksize;
-  const long pitch = 3L * out_w;
-  const unsigned char* p = scratch + d.scratch_offset + (long)first * pitch + 3L * j;
-  int s0 = 1 << (DJ_PATCH_BITS - 1), s1 = s0, s2 = s0;
-  for (int t = 0; t < n; ++t) {
-    const int c = taps[t];
-    s0 += p[t * pitch] * c;
-    s1 += p[t * pitch + 1] * c;
-    s2 += p[t * pitch + 2] * c;
-  }
-  unsigned char* o = out + ((long)blockIdx.y * out_h + y) * out_stride + 3L * j;
-  o[0] = patch_clip8(s0);
-  o[1] = patch_clip8(s1);
-  o[2] = patch_clip8(s2);
-}
-
-// bounds + taps of one axis: `count` pairs at `b_off`, `count` rows of `ksize` taps at `k_off`, all inside the pool, and
-// every sample's taps inside the `size` window samples of that axis
-static int patch_check_axis(const char* axis, int i, long b_off, long k_off, int ksize, int count, int size,
-                            const int* pool_host, long pool_ints) {
-  DJ_CHECK_ARG(ksize >= 1 && ksize <= DJ_PATCH_MAX_SIDE, "patch_resize: image %d: %s tap row length %d outside 1..%d", i, axis,
-               ksize, DJ_PATCH_MAX_SIDE);
-  DJ_CHECK_ARG(b_off >= 0 && b_off + 2L * count <= pool_ints, "patch_resize: image %d: %s bounds [%ld, %ld) leave the pool of %ld",
-               i, axis, b_off, b_off + 2L * count, pool_ints);
-  DJ_CHECK_ARG(k_off >= 0 && k_off + (long)ksize * count <= pool_ints,
-               "patch_resize: image %d: %s taps [%ld, %ld) leave the pool of %ld", i, axis, k_off, k_off + (long)ksize * count,
-               pool_ints);
-  for (int j = 0; j < count; ++j) {
-    const int* b = pool_host + b_off + 2L * j;
-    DJ_CHECK_ARG(b[0] >= 0 && b[1] >= 0 && b[1] <= ksize && (long)b[0] + b[1] <= size,
-                 "patch_resize: image %d: %s sample %d reads window samples [%d, %d + %d) of %d (tap row length %d)", i, axis, j,
-                 b[0], b[0], b[1], size, ksize);
-  }
-  return DJ_OK;
+  dj_vertical_sample(pool + d.v_bounds + 2 * y, pool + d.v_taps + (long)y * d.v_ksize, scratch + d.scratch_offset + 3L * j, 0,
+                     3L * out_w, out + ((long)blockIdx.y * out_h + y) * out_stride + 3L * j);
 }
 
 extern "C" long dj_patch_resize_scratch_bytes(const dj_patch_resize_desc* desc_host, int batch, int out_w) {
@@ -130,7 +87,7 @@ extern "C" long dj_patch_resize_scratch_bytes(const dj_patch_resize_desc* desc_h
       dj_set_error("patch_resize_scratch_bytes: image %d: win_h %d outside 1..%d", i, desc_host[i].win_h, DJ_PATCH_MAX_SIDE);
       return DJ_ERR_ARG;
     }
-    total += (3L * out_w * desc_host[i].win_h + 63) / 64 * 64;
+    total += dj_scratch_region_bytes(3L * out_w * desc_host[i].win_h);
   }
   return total;
 }
@@ -157,31 +114,16 @@ extern "C" int dj_patch_resize(const unsigned char* src, long src_bytes, const d
   int max_rows = 0;
   for (int i = 0; i < batch; ++i) {
     const dj_patch_resize_desc* d = desc_host + i;
-    DJ_CHECK_ARG(d->src_h >= 0 && d->src_w >= 0 && d->src_h <= DJ_PATCH_MAX_SIDE && d->src_w <= DJ_PATCH_MAX_SIDE &&
-                     (d->src_h == 0) == (d->src_w == 0),
-                 "patch_resize: image %d: staged size %d x %d outside 1..%d (0 x 0: nothing staged)", i, d->src_h, d->src_w,
-                 DJ_PATCH_MAX_SIDE);
-    if (d->src_h > 0) {
-      DJ_CHECK_ARG(d->src_stride >= 3L * d->src_w, "patch_resize: image %d: src_stride %ld below 3 * width = %ld", i,
-                   d->src_stride, 3L * d->src_w);
-      DJ_CHECK_ARG(d->src_offset >= 0 && d->src_stride <= src_bytes && d->src_offset <= src_bytes &&
-                       d->src_offset + (d->src_h - 1) * d->src_stride + 3L * d->src_w <= src_bytes,
-                   "patch_resize: image %d: pixels at offset %ld leave the source buffer of %ld bytes", i, d->src_offset,
-                   src_bytes);
-    }
+    if (dj_check_staged_rect("patch_resize", i, d, src_bytes) != DJ_OK) return DJ_ERR_ARG;
     DJ_CHECK_ARG(d->win_h >= 1 && d->win_w >= 1 && d->win_h <= DJ_PATCH_MAX_SIDE && d->win_w <= DJ_PATCH_MAX_SIDE,
                  "patch_resize: image %d: window size %d x %d outside 1..%d", i, d->win_h, d->win_w, DJ_PATCH_MAX_SIDE);
     DJ_CHECK_ARG(d->win_y0 >= -DJ_PATCH_MAX_ORIGIN && d->win_y0 <= DJ_PATCH_MAX_ORIGIN && d->win_x0 >= -DJ_PATCH_MAX_ORIGIN &&
                      d->win_x0 <= DJ_PATCH_MAX_ORIGIN,
                  "patch_resize: image %d: window origin (y %d, x %d) outside +-%d", i, d->win_y0, d->win_x0, DJ_PATCH_MAX_ORIGIN);
-    if (patch_check_axis("horizontal", i, d->h_bounds, d->h_taps, d->h_ksize, out_w, d->win_w, pool_host, pool_ints) != DJ_OK ||
-        patch_check_axis("vertical", i, d->v_bounds, d->v_taps, d->v_ksize, out_h, d->win_h, pool_host, pool_ints) != DJ_OK)
+    if (dj_check_axis("patch_resize", "horizontal", i, d->h_bounds, d->h_taps, d->h_ksize, out_w, pool_ints, pool_host, d->win_w) != DJ_OK ||
+        dj_check_axis("patch_resize", "vertical", i, d->v_bounds, d->v_taps, d->v_ksize, out_h, pool_ints, pool_host, d->win_h) != DJ_OK ||
+        dj_check_scratch_region("patch_resize", i, d->scratch_offset, 3L * out_w * d->win_h, &scratch_end, scratch_bytes) != DJ_OK)
       return DJ_ERR_ARG;
-    const long need = 3L * out_w * d->win_h;
-    DJ_CHECK_ARG(d->scratch_offset >= scratch_end && d->scratch_offset <= scratch_bytes && d->scratch_offset + need <= scratch_bytes,
-                 "patch_resize: image %d: scratch [%ld, + %ld) overlaps image %d's or leaves the buffer of %ld bytes", i,
-                 d->scratch_offset, need, i - 1, scratch_bytes);
-    scratch_end = d->scratch_offset + need;
     if (d->win_h > max_rows) max_rows = d->win_h;
   }
   const dim3 block(DJ_PATCH_THREADS);

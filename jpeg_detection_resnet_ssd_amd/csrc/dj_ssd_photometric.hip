@@ -18,13 +18,11 @@
 // image selects the operations, so every branch on it is uniform over the workgroup.  blockIdx.y is the image, blockIdx.x
 // runs over the largest rectangle's pixels and the blocks past a smaller one leave at once (an image with nothing staged
 // costs only that), as in dj_patchresize.hip.
-#include "../../include/dj_hip.h"
-#include "dj_common.h"
+#include "dj_resample.h"
 
 #pragma clang fp contract(off)
 
 #define DJ_SSDP_THREADS 256
-#define DJ_SSDP_MAX_SIDE 65536            // of a staged rectangle, as dj_patch_resize
 #define DJ_SSDP_SHIFT 12
 #define DJ_SSDP_ALL (DJ_SSD_PHOTO_BRIGHTNESS | DJ_SSD_PHOTO_CONTRAST | DJ_SSD_PHOTO_SATURATION | DJ_SSD_PHOTO_HUE)
 
@@ -130,21 +128,10 @@ extern "C" int dj_ssd_photometric(unsigned char* src, long src_bytes, const dj_p
   for (int i = 0; i < batch; ++i) {
     const dj_patch_resize_desc* d = desc_host + i;
     const dj_ssd_photo_params* q = params_host + i;
-    DJ_CHECK_ARG(d->src_h >= 0 && d->src_w >= 0 && d->src_h <= DJ_SSDP_MAX_SIDE && d->src_w <= DJ_SSDP_MAX_SIDE &&
-                     (d->src_h == 0) == (d->src_w == 0),
-                 "ssd_photometric: image %d: staged size %d x %d outside 1..%d (0 x 0: nothing staged)", i, d->src_h, d->src_w,
-                 DJ_SSDP_MAX_SIDE);
+    if (dj_check_staged_rect("ssd_photometric", i, d, src_bytes) != DJ_OK) return DJ_ERR_ARG;
     const long pixels = (long)d->src_h * d->src_w;
     DJ_CHECK_ARG(pixels <= 0x7fffffffL, "ssd_photometric: image %d: %d x %d staged pixels, at most 2^31 - 1 are supported", i,
                  d->src_h, d->src_w);
-    if (d->src_h > 0) {
-      DJ_CHECK_ARG(d->src_stride >= 3L * d->src_w, "ssd_photometric: image %d: src_stride %ld below 3 * width = %ld", i,
-                   d->src_stride, 3L * d->src_w);
-      DJ_CHECK_ARG(d->src_offset >= 0 && d->src_stride <= src_bytes && d->src_offset <= src_bytes &&
-                       d->src_offset + (d->src_h - 1) * d->src_stride + 3L * d->src_w <= src_bytes,
-                   "ssd_photometric: image %d: pixels at offset %ld leave the source buffer of %ld bytes", i, d->src_offset,
-                   src_bytes);
-    }
     DJ_CHECK_ARG(q->sequence == 1 || q->sequence == 2, "ssd_photometric: image %d: sequence %d is neither 1 nor 2", i,
                  q->sequence);
     DJ_CHECK_ARG((q->flags & ~DJ_SSDP_ALL) == 0, "ssd_photometric: image %d: flags 0x%x name an unknown operation", i, q->flags);

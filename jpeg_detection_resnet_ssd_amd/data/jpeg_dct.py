@@ -5,7 +5,9 @@ reader in place of jpeg2dct and the whole batch decoded by host threads into flo
 
 The same numbers are a pure integer function of the pixels, so the step also exists without a JPEG file in between:
 `rgb_to_dct_host` states that function in numpy and `DeviceDCTEmitter` / `emit_dct_inputs_device` run it on the GPU
-(csrc/dj_rgb2dct.hip), bit-exact with the PIL + reader path (tests/test_rgb_dct_cpu.py, tests/test_rgb_dct_gpu.py)."""
+(csrc/dj_rgb2dct.hip), bit-exact with the PIL + reader path (tests/test_rgb_dct_cpu.py, tests/test_rgb_dct_gpu.py).
+`PendingInputs` is the protocol by which a batch reaches a model's resident input buffers through that kernel; the batches
+of data/image_prep.py and data/patch_resize.py, which first make their pixels on the GPU, derive from it too."""
 import io
 
 import numpy as np
@@ -53,7 +55,7 @@ def quant_tables(quality=75):
                  for base in (sd._LUMA_BASE, sd._CHROMA_BASE))
 
 
-def _resolve_tables(quality, tables):
+def resolve_tables(quality, tables):
     if tables is None:
         return quant_tables(quality)
     luma, chroma = (np.asarray(t).reshape(-1) for t in tables)
@@ -119,7 +121,7 @@ def rgb_to_dct_host(image, quality=75, tables=None, normalized=True):
     image = np.asarray(image)
     if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8 or image.shape[0] < 1 or image.shape[1] < 1:
         raise ValueError("expected an (H, W, 3) uint8 image, got %s %s" % (image.dtype, image.shape))
-    luma, chroma = _resolve_tables(quality, tables)
+    luma, chroma = resolve_tables(quality, tables)
     h, w = image.shape[:2]
     r, g, b = (image[..., i].astype(np.int32) for i in range(3))
     y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
@@ -150,58 +152,78 @@ def input_shapes(batch, height, width, deconv=False):
     return [(batch, yh, yw, 64), (batch, ch, cw, 128)]
 
 
-class PendingDCTInputs(object):
-    """The pixels of one batch, to be transformed straight into a model's resident input buffers at upload time
-    (`Model.train_on_batch / predict_on_batch / predict / fit_generator` accept it where they accept the list of input
-    arrays)."""
+def emit_resident(pixels, tables, deconv, buffers):
+    """dj_rgb_to_dct of a resident (B, H, W, 3) uint8 CUDA batch into `buffers` ([Y, CbCr], or [Y, Cb, Cr] when `deconv`),
+    on the current stream."""
+    from .. import kernels
+    outs = tuple(buffers) if deconv else (buffers[0], buffers[1][..., :64], buffers[1][..., 64:])
+    kernels.rgb_to_dct(pixels, tables, outs, normalized=True)
+    return buffers
 
-    def __init__(self, emitter, batch_X):
-        x = np.ascontiguousarray(np.asarray(batch_X))
-        if x.ndim != 4 or x.shape[3] != 3 or x.dtype != np.uint8:
-            raise ValueError("expected a (B, H, W, 3) uint8 batch, got %s %s" % (x.dtype, x.shape))
-        self.emitter = emitter
-        self.pixels = x
+
+class PendingInputs(object):
+    """One batch on its way into a model's resident input buffers, transformed at upload time (`Model.train_on_batch /
+    predict_on_batch / predict / fit_generator` accept it where they accept the list of input arrays).  `emitter` carries
+    `tables` and `deconv`; `shape` is that of the pixel batch the model sees (`shape[0]` is the batch size, as for the
+    first array of an input list).  A subclass provides `sliced(index)`, `host_pixels()` (the uint8 batch computed on the
+    host) and `resident_pixels(device)` (the same batch as a uint8 CUDA tensor, made on the current stream)."""
+
+    def __init__(self, emitter, shape):
+        self.emitter, self.shape = emitter, tuple(shape)
 
     def __len__(self):
-        return self.pixels.shape[0]
-
-    @property
-    def shape(self):
-        """Of the pixel batch: `shape[0]` is the batch size, as for the first array of an input list."""
-        return self.pixels.shape
+        return self.shape[0]
 
     def __getitem__(self, index):
         if not isinstance(index, slice):
-            raise TypeError("PendingDCTInputs can only be sliced along the batch")
-        return PendingDCTInputs(self.emitter, self.pixels[index])
+            raise TypeError("%s can only be sliced along the batch" % type(self).__name__)
+        return self.sliced(index)
 
     @property
     def shapes(self):
-        b, h, w, _ = self.pixels.shape
+        b, h, w, _ = self.shape
         return input_shapes(b, h, w, self.emitter.deconv)
 
     def emit_into(self, buffers):
-        """Upload the uint8 pixels and launch the transform on the current stream, writing into `buffers`: float32
+        """Make the uint8 batch resident and launch the transform on the current stream, writing into `buffers`: float32
         CUDA tensors of `self.shapes` ([Y, CbCr] or [Y, Cb, Cr])."""
-        import torch
-        from .. import kernels
         buffers = list(buffers)
         if [tuple(t.shape) for t in buffers] != [tuple(s) for s in self.shapes]:
             raise ValueError("emit_into: expected buffers of shapes %s, got %s"
                              % (self.shapes, [tuple(t.shape) for t in buffers]))
-        dev = torch.from_numpy(self.pixels).to(buffers[0].device, non_blocking=True)
-        if self.emitter.deconv:
-            outs = tuple(buffers)
-        else:
-            outs = (buffers[0], buffers[1][..., :64], buffers[1][..., 64:])
-        kernels.rgb_to_dct(dev, self.emitter.tables, outs, normalized=True)
-        return buffers
+        return emit_resident(self.resident_pixels(buffers[0].device), self.emitter.tables, self.emitter.deconv, buffers)
 
     def numpy(self):
-        """The same inputs computed on the host (`rgb_to_dct_host` per image), float32."""
-        planes = [rgb_to_dct_host(img, tables=self.emitter.tables) for img in self.pixels]
+        """The same inputs computed on the host (`host_pixels`, then `rgb_to_dct_host` per image), float32."""
+        planes = [rgb_to_dct_host(img, tables=self.emitter.tables) for img in self.host_pixels()]
         y, cb, cr = (np.stack([p[i] for p in planes]).astype(np.float32) for i in range(3))
         return [y, cb, cr] if self.emitter.deconv else [y, np.concatenate([cb, cr], axis=-1)]
+
+
+def check_batch(batch_X):
+    x = np.ascontiguousarray(np.asarray(batch_X))
+    if x.ndim != 4 or x.shape[3] != 3 or x.dtype != np.uint8:
+        raise ValueError("expected a (B, H, W, 3) uint8 batch, got %s %s" % (x.dtype, x.shape))
+    return x
+
+
+class PendingDCTInputs(PendingInputs):
+    """The pixels of one batch, to be transformed straight into a model's resident input buffers at upload time: one
+    upload of the uint8 pixels, then dj_rgb_to_dct."""
+
+    def __init__(self, emitter, batch_X):
+        self.pixels = check_batch(batch_X)
+        PendingInputs.__init__(self, emitter, self.pixels.shape)
+
+    def sliced(self, index):
+        return PendingDCTInputs(self.emitter, self.pixels[index])
+
+    def host_pixels(self):
+        return self.pixels
+
+    def resident_pixels(self, device):
+        import torch
+        return torch.from_numpy(self.pixels).to(device, non_blocking=True)
 
 
 class DeviceDCTEmitter(object):
@@ -211,7 +233,7 @@ class DeviceDCTEmitter(object):
     the targets).  `quality` as in `Image.save(..., quality=)` (PIL's default 75), or two natural-order `tables`."""
 
     def __init__(self, quality=75, tables=None, deconv=False):
-        self.tables = _resolve_tables(quality, tables)
+        self.tables = resolve_tables(quality, tables)
         self.quality = None if tables is not None else int(quality)
         self.deconv = bool(deconv)
 
@@ -223,17 +245,11 @@ def emit_dct_inputs_device(batch_X, deconv=False, quality=75, tables=None, devic
     """`emit_dct_inputs` on the GPU: (B, H, W, 3) uint8 (numpy, or a CUDA tensor already resident) -> `[X_y, X_cbcr]`
     or `[X_y, X_cb, X_cr]` as float32 CUDA tensors, for callers outside `Model`."""
     import torch
-    from .. import kernels
-    tabs = _resolve_tables(quality, tables)
+    tabs = resolve_tables(quality, tables)
     if isinstance(batch_X, torch.Tensor):
         dev = batch_X
     else:
-        x = np.ascontiguousarray(np.asarray(batch_X))
-        if x.ndim != 4 or x.shape[3] != 3 or x.dtype != np.uint8:
-            raise ValueError("expected a (B, H, W, 3) uint8 batch, got %s %s" % (x.dtype, x.shape))
-        dev = torch.from_numpy(x).to(device if device is not None else "cuda", non_blocking=True)
+        dev = torch.from_numpy(check_batch(batch_X)).to(device if device is not None else "cuda", non_blocking=True)
     b, h, w, _ = dev.shape
     bufs = [torch.empty(s, dtype=torch.float32, device=dev.device) for s in input_shapes(b, h, w, deconv)]
-    outs = tuple(bufs) if deconv else (bufs[0], bufs[1][..., :64], bufs[1][..., 64:])
-    kernels.rgb_to_dct(dev, tabs, outs, normalized=True)
-    return bufs
+    return emit_resident(dev, tabs, deconv, bufs)

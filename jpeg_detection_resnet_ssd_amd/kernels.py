@@ -360,6 +360,38 @@ def rgb_to_dct(rgb_u8, tables, outs, normalized=True, stream=None):
     return outs
 
 
+# ---- the staged blobs of data/device_staging.py ------------------------------------------------------------------------------
+def _check_staged(desc_host, dtype, struct, desc_dev, bytes_1d, pool=None):
+    """What dj_image_prep, dj_patch_resize and dj_ssd_photometric take of a staged blob: `desc_host` a numpy array of
+    `dtype` (laid out as the ctypes `struct`), `desc_dev` its bytes on the device, `bytes_1d` the other 1-D uint8 CUDA
+    tensors as (tensor, name) pairs and `pool` = (pool_dev, pool_host) where the entry point reads one -> the batch size."""
+    import ctypes
+    import numpy as np
+    assert dtype.itemsize == ctypes.sizeof(struct), "descriptor layouts disagree"
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == dtype and desc_host.ndim == 1 \
+        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
+    if pool is not None:
+        assert isinstance(pool[1], np.ndarray) and pool[1].dtype == np.int32 and pool[1].ndim == 1 \
+            and pool[1].flags.c_contiguous, "pool_host: expected a contiguous 1-D int32 array"
+    for t, name in bytes_1d:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
+            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
+    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
+    if pool is not None:
+        assert pool[0].is_cuda and pool[0].dtype == torch.int32 and pool[0].dim() == 1 and pool[0].is_contiguous() \
+            and pool[0].numel() >= pool[1].size, "pool_dev: expected a contiguous 1-D int32 CUDA tensor of the pool's size"
+    return desc_host.shape[0]
+
+
+def _packed_rgb_stride(t, what=""):
+    """Row pitch in bytes of a (B, H, W, 3) uint8 tensor of packed RGB pixels whose rows may be strided (images dense)."""
+    b, h, w, _ = t.shape
+    assert t.stride(3) == 1 and (w == 1 or t.stride(2) == 3), what + "pixels must be packed RGB"
+    stride = t.stride(1) if h > 1 else (t.stride(0) if b > 1 else 3 * w)      # one row per image: its pitch is the image pitch
+    assert stride >= 3 * w and (b == 1 or t.stride(0) == h * stride), what + "images must be dense"
+    return stride
+
+
 # ---- ragged batch of decoded images -> resized, cropped, flipped uint8 batch -------------------------------------------------
 def image_prep(src, desc_dev, desc_host, pool_dev, pool_host, target, out, scratch, stream=None):
     """dj_image_prep: `src` 1-D uint8 CUDA tensor holding the source images, `desc_dev` the descriptors' bytes on the
@@ -367,28 +399,14 @@ def image_prep(src, desc_dev, desc_host, pool_dev, pool_host, target, out, scrat
     the int32 bounds-and-taps pool as a CUDA tensor and as a numpy array, `out` a (B, target, target, 3) uint8 CUDA tensor
     whose rows may be strided (images dense), `scratch` a 1-D uint8 CUDA tensor of at least `image_prep_scratch_bytes`
     laid out as the descriptors say.  `stream`: a HIP stream handle (None: the current launch stream)."""
-    import ctypes
-    import numpy as np
     from ._lib import ImagePrepDesc
     from .data.image_prep import DESC_DTYPE
-    assert DESC_DTYPE.itemsize == ctypes.sizeof(ImagePrepDesc), "descriptor layouts disagree"
-    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
-        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
-    b = desc_host.shape[0]
-    assert isinstance(pool_host, np.ndarray) and pool_host.dtype == np.int32 and pool_host.ndim == 1 \
-        and pool_host.flags.c_contiguous, "pool_host: expected a contiguous 1-D int32 array"
-    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
-            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
-    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
-    assert pool_dev.is_cuda and pool_dev.dtype == torch.int32 and pool_dev.dim() == 1 and pool_dev.is_contiguous() \
-        and pool_dev.numel() >= pool_host.size, "pool_dev: expected a contiguous 1-D int32 CUDA tensor of the pool's size"
+    b = _check_staged(desc_host, DESC_DTYPE, ImagePrepDesc, desc_dev, ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")),
+                      (pool_dev, pool_host))
     target = int(target)
     assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (b, target, target, 3), \
         "out: expected uint8 %s, got %s %s" % ((b, target, target, 3), out.dtype, tuple(out.shape))
-    assert out.stride(3) == 1 and (target == 1 or out.stride(2) == 3), "out: pixels must be packed RGB"
-    stride = out.stride(1) if target > 1 else 3 * target
-    assert b == 1 or out.stride(0) == target * stride, "out: images must be dense"
+    stride = _packed_rgb_stride(out, "out: ")
     check(_L().dj_image_prep(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, b, ptr(pool_dev),
                              pool_host.ctypes.data, pool_host.size, target, ptr(out), stride, ptr(scratch), scratch.numel(),
                              stream if stream is not None else _stream()), "dj_image_prep")
@@ -420,9 +438,7 @@ def photometric(pixels, ops_dev, ops_host, shift_out=None, stream=None):
     assert ops_dev.is_cuda and ops_dev.dtype == torch.uint8 and ops_dev.dim() == 1 and ops_dev.is_contiguous() \
         and ops_dev.numel() >= ops_host.nbytes and ops_dev.data_ptr() % 8 == 0, \
         "ops_dev: expected a contiguous, 8-byte aligned 1-D uint8 CUDA tensor of the lists' size"
-    assert pixels.stride(3) == 1 and (w == 1 or pixels.stride(2) == 3), "pixels must be packed RGB"
-    stride = pixels.stride(1) if h > 1 else (pixels.stride(0) if b > 1 else 3 * w)      # one row per image: its pitch is the image pitch
-    assert stride >= 3 * w and (b == 1 or pixels.stride(0) == h * stride), "images must be dense"
+    stride = _packed_rgb_stride(pixels)
     if shift_out is not None:
         assert shift_out.is_cuda and shift_out.dtype == torch.float64 and tuple(shift_out.shape) == (b, 3) \
             and shift_out.is_contiguous(), "shift_out: expected a contiguous (B, 3) float64 CUDA tensor"
@@ -439,28 +455,14 @@ def patch_resize(src, desc_dev, desc_host, pool_dev, pool_host, out, scratch, st
     CUDA tensor whose rows may be strided (images dense), `scratch` a 1-D uint8 CUDA tensor of at least
     `patch_resize_scratch_bytes` laid out as the descriptors say.  `stream`: a HIP stream handle (None: the current launch
     stream)."""
-    import ctypes
-    import numpy as np
     from ._lib import PatchResizeDesc
     from .data.patch_resize import DESC_DTYPE
-    assert DESC_DTYPE.itemsize == ctypes.sizeof(PatchResizeDesc), "descriptor layouts disagree"
-    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
-        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
-    b = desc_host.shape[0]
-    assert isinstance(pool_host, np.ndarray) and pool_host.dtype == np.int32 and pool_host.ndim == 1 \
-        and pool_host.flags.c_contiguous, "pool_host: expected a contiguous 1-D int32 array"
-    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
-            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
-    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
-    assert pool_dev.is_cuda and pool_dev.dtype == torch.int32 and pool_dev.dim() == 1 and pool_dev.is_contiguous() \
-        and pool_dev.numel() >= pool_host.size, "pool_dev: expected a contiguous 1-D int32 CUDA tensor of the pool's size"
+    b = _check_staged(desc_host, DESC_DTYPE, PatchResizeDesc, desc_dev, ((src, "src"), (desc_dev, "desc_dev"), (scratch, "scratch")),
+                      (pool_dev, pool_host))
     assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 4 and out.shape[0] == b and out.shape[3] == 3, \
         "out: expected a (%d, out_h, out_w, 3) uint8 CUDA tensor, got %s %s" % (b, out.dtype, tuple(out.shape))
     out_h, out_w = int(out.shape[1]), int(out.shape[2])
-    assert out.stride(3) == 1 and (out_w == 1 or out.stride(2) == 3), "out: pixels must be packed RGB"
-    stride = out.stride(1) if out_h > 1 else (out.stride(0) if b > 1 else 3 * out_w)      # one row per image: its pitch is the image pitch
-    assert stride >= 3 * out_w and (b == 1 or out.stride(0) == out_h * stride), "out: images must be dense"
+    stride = _packed_rgb_stride(out, "out: ")
     check(_L().dj_patch_resize(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, b, ptr(pool_dev),
                                pool_host.ctypes.data, pool_host.size, out_h, out_w, ptr(out), stride, ptr(scratch),
                                scratch.numel(), stream if stream is not None else _stream()), "dj_patch_resize")
@@ -484,17 +486,10 @@ def ssd_photometric(src, desc_dev, desc_host, params_dev, params_host, stream=No
     from ._lib import PatchResizeDesc, SsdPhotoParams
     from .data.patch_resize import DESC_DTYPE
     from .data.ssd_photometric import PARAMS_DTYPE
-    assert DESC_DTYPE.itemsize == ctypes.sizeof(PatchResizeDesc), "descriptor layouts disagree"
+    b = _check_staged(desc_host, DESC_DTYPE, PatchResizeDesc, desc_dev, ((src, "src"), (desc_dev, "desc_dev"), (params_dev, "params_dev")))
     assert PARAMS_DTYPE.itemsize == ctypes.sizeof(SsdPhotoParams), "parameter-record layouts disagree"
-    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.ndim == 1 \
-        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous 1-D array of DESC_DTYPE"
-    b = desc_host.shape[0]
     assert isinstance(params_host, np.ndarray) and params_host.dtype == PARAMS_DTYPE and params_host.shape == (b,) \
         and params_host.flags.c_contiguous, "params_host: expected a contiguous array of one PARAMS_DTYPE record per image"
-    for t, name in ((src, "src"), (desc_dev, "desc_dev"), (params_dev, "params_dev")):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous(), \
-            "%s: expected a contiguous 1-D uint8 CUDA tensor" % name
-    assert desc_dev.numel() >= desc_host.nbytes and desc_dev.data_ptr() % 8 == 0, "desc_dev: too small or misaligned"
     assert params_dev.numel() >= params_host.nbytes and params_dev.data_ptr() % 4 == 0, "params_dev: too small or misaligned"
     check(_L().dj_ssd_photometric(ptr(src), src.numel(), ptr(desc_dev), desc_host.ctypes.data, ptr(params_dev),
                                   params_host.ctypes.data, b, stream if stream is not None else _stream()),

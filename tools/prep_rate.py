@@ -161,7 +161,7 @@ def main():
     scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
     host = staging.numpy()
     reps = max(50, args.reps)
-    prep_ms = event_ms(lambda: image_prep._run_plan(plan, host, blob, pixels, scratch), reps)
+    prep_ms = event_ms(lambda: plan.launch(host, blob, pixels, scratch), reps)
     outs = tuple(bufs)
     dct_ms = event_ms(lambda: kernels.rgb_to_dct(pixels, prep.tables, outs), reps)
     d = plan.desc
@@ -179,7 +179,7 @@ def main():
     res["device_photometric_emit_only_ms"] = median_ms(lambda: with_ops.emit_into(bufs), args.reps)
     ops_host = with_ops.plan.ops
     ops_dev = torch.from_numpy(ops_host.view(np.uint8).reshape(-1).copy()).to(dev)
-    image_prep._run_plan(plan, host, blob, pixels, scratch)
+    plan.launch(host, blob, pixels, scratch)
     prepared_dev = pixels.clone()
 
     def restore():          # the kernel works in place: every repetition starts from the prepared batch again

@@ -144,7 +144,7 @@ def main():
     scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
     host = staging.numpy()
     reps = max(50, args.reps)
-    patch_ms = event_ms(lambda: patch_resize._run_plan(plan, host, blob, pixels, scratch), reps)
+    patch_ms = event_ms(lambda: plan.launch(host, blob, pixels, scratch), reps)
     outs = tuple(bufs)
     dct_ms = event_ms(lambda: kernels.rgb_to_dct(pixels, prep.tables, outs), reps)
     d = plan.desc
@@ -191,7 +191,7 @@ def main():
     res["ssd_photometric_ms"], res["ssd_photometric_bytes"] = photo_ms, photo_bytes
     res["ssd_photometric_GBs"] = photo_bytes / photo_ms[0] / 1e6
     scratch_p = torch.empty(plan_p.scratch_bytes, dtype=torch.uint8, device=dev)
-    res["photometric_plus_patch_resize_ms"] = event_ms(lambda: patch_resize._run_plan(plan_p, host_p, blob_p, pixels, scratch_p), reps)
+    res["photometric_plus_patch_resize_ms"] = event_ms(lambda: plan_p.launch(host_p, blob_p, pixels, scratch_p), reps)
     res["mean_taps"] = [float(np.mean([plan.pool[int(x["h_bounds"]) + 1:int(x["h_bounds"]) + 2 * OUT:2].mean() for x in d])),
                         float(np.mean([plan.pool[int(x["v_bounds"]) + 1:int(x["v_bounds"]) + 2 * OUT:2].mean() for x in d]))]
     res["h_grid_fill"] = float(rows.mean() / rows.max())      # share of the horizontal pass's blocks that have work

@@ -3,6 +3,8 @@
 localisation_part/evaluation.py (same positional `weights`, `--archi`, dataset flags; `-r/--ssd_resnet` is the only
 model family built here), `mode='inference'` model with the on-device DecodeDetections layer, `Evaluator(...)` with the
 reference's settings (evaluation.py:102-131: batch 8, 'resize', 11-point sampling, IoU 0.5, 'include' borders).
+Matching, precision / recall and AP run on the GPU (csrc/dj_eval.hip, results equal bit for bit to the host loop, equal
+confidences ranked in list order); `--host_matching` restores the host loop.
 The VOC XML/JPEG dataset readers are out of scope; `--generator module:factory` plugs one in, the default is
 the synthetic JPEG-DCT dataset."""
 import importlib
@@ -27,6 +29,8 @@ parser.add_argument("--archi", default="ssd_custom")
 parser.add_argument("--generator", default=None, help="module:factory returning a DataGenerator-like evaluation dataset")
 parser.add_argument("--synthetic_images", type=int, default=64)
 parser.add_argument("--batch_size", type=int, default=8)
+parser.add_argument("--host_matching", action="store_true", default=False,
+                    help="match predictions and compute precision / recall / AP with the host numpy loop instead of the GPU")
 args = parser.parse_args()
 if args.ssd or args.ssd_other or args.ssd_dct or args.ssd_miisst or args.ssd_miisst_dct:
     raise SystemExit("only the ResNet50-DCT SSD family (-r, --archi ...) is built here; the VGG models are out of scope")
@@ -68,7 +72,8 @@ if args.archi == "deconv":
 
 classes = ["background", "aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow",
            "diningtable", "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor"]
-evaluator = Evaluator(model=model, n_classes=n_classes, data_generator=dataset, model_mode=model_mode)
+evaluator = Evaluator(model=model, n_classes=n_classes, data_generator=dataset, model_mode=model_mode,
+                      device_matching=not args.host_matching)
 results = evaluator(img_height=img_height, img_width=img_width, batch_size=args.batch_size, data_generator_mode="resize",
                     round_confidences=False, matching_iou_threshold=0.5, border_pixels="include",
                     sorting_algorithm="quicksort", average_precision_mode="sample", num_recall_points=11,

@@ -540,6 +540,34 @@ int dj_ssd_photometric(unsigned char* src, long src_bytes, const dj_patch_resize
                        const dj_patch_resize_desc* desc_host, const dj_ssd_photo_params* params_dev,
                        const dj_ssd_photo_params* params_host, int batch, void* stream);
 
+/* ---- Pascal-VOC evaluation (L/eval_utils/average_precision_evaluator.py:570-925): `Evaluator.match_predictions`,
+ * `compute_precision_recall` and `compute_average_precisions(mode='sample')` with results equal bit for bit to the host
+ * methods (float64, their operation order; eval_utils/device_matching.py packs the inputs and restates the segment-wise
+ * computation in numpy).  All pointers are DEVICE pointers.
+ * Predictions of classes 1..n_classes lie one class after another, each class in rank order (confidence descending, equal
+ * confidences in list order): class c occupies [class_offsets[c], class_offsets[c + 1]) of pred_boxes [n_pred][4] =
+ * (xmin, ymin, xmax, ymax) float32 and of every per-prediction output; class_offsets has n_classes + 2 entries.  A segment
+ * is one (class, image) pair with predictions: seg_ranks[seg_offsets[s] .. seg_offsets[s + 1]) holds their ranks within
+ * the class, increasing.  Ground truth: gt_boxes [n_gt][4] float64, gt_class, gt_neutral (bytes), image i owning rows
+ * [gt_offsets[i], gt_offsets[i + 1]), at most 4096 per image (max_gt_per_image is the caller's maximum, checked).
+ * dj_eval_match: one wave per segment walks its predictions in rank order; IoU as iou(gt, pred, coords='corners',
+ * mode='element-wise', border_pixels), np.argmax over the image's rows of the class (first maximum, a NaN wins), then
+ * false positive when there is no such row or best < matching_iou_threshold, nothing when the row is neutral and
+ * use_neutral != 0, true positive when the row is free (it is taken then), false positive otherwise.  tp / fp [n_pred]
+ * int32 receive the flags at class_offsets[c] + rank; the caller zeroes them first.
+ * dj_eval_precision_recall_ap: one block per class: cum_tp / cum_fp (running sums of the flags), precision = tp / (tp + fp)
+ * where tp + fp > 0 else 0, recall = tp / num_gt[c] (num_gt: n_classes + 1 doubles), and ap[c] (n_classes + 1 doubles,
+ * entry 0 untouched) = (sum over the num_recall_points <= 1024 thresholds t, in order, of max{precision : recall >= t} or 0)
+ * / num_recall_points.  Both are one launch without synchronisation. ---- */
+int dj_eval_match(const float* pred_boxes, const int* seg_ranks, const int* seg_offsets, const int* seg_class,
+                  const int* seg_image, int n_segments, const int* class_offsets, int n_classes, int n_pred,
+                  const double* gt_boxes, const int* gt_class, const unsigned char* gt_neutral, const int* gt_offsets,
+                  int n_images, int n_gt, int max_gt_per_image, int use_neutral, double matching_iou_threshold,
+                  int border_pixels, int* tp, int* fp, void* stream);
+int dj_eval_precision_recall_ap(const int* tp, const int* fp, const int* class_offsets, int n_classes, int n_pred,
+                                const double* num_gt, const double* thresholds, int num_recall_points, int* cum_tp,
+                                int* cum_fp, double* precision, double* recall, double* ap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

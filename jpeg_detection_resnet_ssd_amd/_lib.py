@@ -177,6 +177,11 @@ SIGNATURES = {
     "dj_patch_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
                                 c_long, c_void_p, c_long, c_void_p]),
     "dj_ssd_photometric": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dj_eval_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
+                              c_void_p]),
+    "dj_eval_precision_recall_ap": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

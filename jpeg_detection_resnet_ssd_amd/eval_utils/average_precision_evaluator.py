@@ -7,7 +7,10 @@ localisation_part/eval_utils/average_precision_evaluator.py:32-947 (`Evaluator._
 Parity unpinned: the reference module cannot be imported here (it pulls cv2 / bs4 / h5py through the data generator),
 so the known answers in tests/test_evaluator_cpu.py are hand-derived from the VOC definitions.  One deliberate
 difference: the reference iterates `range(len(predictions.shape))` (= 1 prediction) when verbose=False
-(:699); here every prediction is matched regardless of `verbose`."""
+(:699); here every prediction is matched regardless of `verbose`.
+
+`Evaluator(device_matching=True)` computes the matching, precision / recall and sampled AP on the GPU instead
+(device_matching.py, csrc/dj_eval.hip); the host methods below are the statement those results are equal to."""
 from math import ceil
 
 import numpy as np
@@ -19,7 +22,8 @@ from ..ssd_encoder_decoder.ssd_output_decoder import decode_detections
 class Evaluator(object):
     def __init__(self, model, n_classes, data_generator, model_mode="inference",
                  pred_format={"class_id": 0, "conf": 1, "xmin": 2, "ymin": 3, "xmax": 4, "ymax": 5},
-                 gt_format={"class_id": 0, "xmin": 1, "ymin": 2, "xmax": 3, "ymax": 4}, ignore_under_area=0):
+                 gt_format={"class_id": 0, "xmin": 1, "ymin": 2, "xmax": 3, "ymax": 4}, ignore_under_area=0,
+                 device_matching=False):
         self.model = model
         self.data_generator = data_generator
         self.n_classes = n_classes
@@ -27,6 +31,10 @@ class Evaluator(object):
         self.pred_format = pred_format
         self.gt_format = gt_format
         self.ignore_under_area = ignore_under_area
+        # True: match_predictions, compute_precision_recall and compute_average_precisions run on the GPU
+        # (eval_utils/device_matching.py, csrc/dj_eval.hip) and leave the same values in the same attributes
+        self.device_matching = device_matching
+        self._device_eval = None
         self.prediction_results = None
         self.num_gt_per_class = None
         self.true_positives = None
@@ -167,6 +175,8 @@ class Evaluator(object):
             raise ValueError("Matching predictions to ground truth boxes not possible, no ground truth given.")
         if self.prediction_results is None:
             raise ValueError("There are no prediction results. You must run `predict_on_dataset()` before calling this method.")
+        if self.device_matching:
+            return self._match_predictions_device(ignore_neutral_boxes, matching_iou_threshold, border_pixels, verbose, ret)
         g = self.gt_format
         neutral_known = getattr(self.data_generator, "eval_neutral", None) is not None
         use_neutral = ignore_neutral_boxes and neutral_known
@@ -234,6 +244,8 @@ class Evaluator(object):
             raise ValueError("True and false positives not available. You must run `match_predictions()` before you call this method.")
         if self.num_gt_per_class is None:
             raise ValueError("Number of ground truth boxes per class not available. You must run `get_num_gt_per_class()` before you call this method.")
+        if self.device_matching:
+            return self._compute_precision_recall_device(ret)
         cumulative_precisions, cumulative_recalls = [[]], [[]]
         for class_id in range(1, self.n_classes + 1):
             tp = np.asarray(self.cumulative_true_positives[class_id], dtype=float)
@@ -250,6 +262,8 @@ class Evaluator(object):
             raise ValueError("Precisions and recalls not available. You must run `compute_precision_recall()` before you call this method.")
         if mode not in {"sample", "integrate"}:
             raise ValueError("`mode` can be either 'sample' or 'integrate', but received '{}'".format(mode))
+        if self.device_matching and mode == "sample" and num_recall_points >= 1:
+            return self._compute_average_precisions_device(num_recall_points, ret)
         average_precisions = [0.0]
         for class_id in range(1, self.n_classes + 1):
             prec = np.asarray(self.cumulative_precisions[class_id], dtype=float)
@@ -272,6 +286,67 @@ class Evaluator(object):
         self.average_precisions = average_precisions
         if ret:
             return average_precisions
+
+    # ---- the device path (device_matching=True) ------------------------------------------------------------------------
+    def _match_predictions_device(self, ignore_neutral_boxes, matching_iou_threshold, border_pixels, verbose, ret):
+        """`match_predictions` on the GPU.  The rank order is device_matching.pack_evaluation's: confidence descending,
+        equal confidences in list order ("mergesort"), whatever `sorting_algorithm` says."""
+        from .device_matching import DeviceEvaluation, pack_evaluation
+        if border_pixels not in ("half", "include", "exclude"):
+            raise ValueError("Unexpected value for `border_pixels`: '{}'".format(border_pixels))
+        if verbose:
+            for class_id in range(1, self.n_classes + 1):
+                if len(self.prediction_results[class_id]) == 0:
+                    print("No predictions for class {}/{}".format(class_id, self.n_classes))
+        dev = DeviceEvaluation(pack_evaluation(self, ignore_neutral_boxes))
+        dev.upload()
+        tp, fp = dev.match(matching_iou_threshold, border_pixels)
+        cum_tp, cum_fp = dev.precision_recall_ap(None, 1)[:2]
+        self.true_positives, self.false_positives = dev.per_class(tp, int), dev.per_class(fp, int)
+        self.cumulative_true_positives = dev.per_class(cum_tp, int)
+        self.cumulative_false_positives = dev.per_class(cum_fp, int)
+        # the flags stay on the device for the next two stages, for as long as these very lists are the Evaluator's
+        self._device_eval = (dev, self.true_positives, self.false_positives)
+        if ret:
+            return (self.true_positives, self.false_positives, self.cumulative_true_positives,
+                    self.cumulative_false_positives)
+
+    def _device_flags(self):
+        """The DeviceEvaluation holding the flags of `self.true_positives` / `self.false_positives`: the cached one when
+        it was made from these lists, else one that uploads them."""
+        from .device_matching import DeviceEvaluation
+        cached = self._device_eval
+        if cached is None or cached[1] is not self.true_positives or cached[2] is not self.false_positives:
+            if self.true_positives is None or self.false_positives is None:
+                raise ValueError("True and false positives not available. You must run `match_predictions()` before you call this method.")
+            cached = (DeviceEvaluation.from_flags(self.true_positives, self.false_positives), self.true_positives,
+                      self.false_positives)
+            self._device_eval = cached
+        return cached[0]
+
+    def _compute_precision_recall_device(self, ret):
+        dev = self._device_flags()
+        _, _, precision, recall, _ = dev.precision_recall_ap(self.num_gt_per_class, 1)
+        self.cumulative_precisions, self.cumulative_recalls = dev.per_class(precision, float), dev.per_class(recall, float)
+        # the sampled AP is computed from these curves: it uses the counts they were made with
+        self._device_curves = (self.cumulative_precisions, np.array(self.num_gt_per_class))
+        if ret:
+            return self.cumulative_precisions, self.cumulative_recalls
+
+    def _compute_average_precisions_device(self, num_recall_points, ret):
+        dev = self._device_flags()
+        curves = getattr(self, "_device_curves", None)
+        num_gt = curves[1] if curves is not None and curves[0] is self.cumulative_precisions else self.num_gt_per_class
+        ap = dev.precision_recall_ap(num_gt, num_recall_points)[4].cpu().numpy()
+        # the host's sum starts as the python float 0.0 and becomes an np.float64 with the first maximum it adds: a class
+        # none of whose recalls reaches the lowest threshold (no predictions, or recall 0/0) keeps the python float
+        t_min = np.linspace(0, 1, num_recall_points, endpoint=True).min()
+        with np.errstate(invalid="ignore"):
+            reached = [bool(np.any(np.asarray(self.cumulative_recalls[c], dtype=float) >= t_min))
+                       for c in range(1, self.n_classes + 1)]
+        self.average_precisions = [0.0] + [ap[c] if r else 0.0 for c, r in zip(range(1, self.n_classes + 1), reached)]
+        if ret:
+            return self.average_precisions
 
     def compute_mean_average_precision(self, ret=True):
         if self.average_precisions is None:

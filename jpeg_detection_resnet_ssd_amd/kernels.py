@@ -495,3 +495,50 @@ def ssd_photometric(src, desc_dev, desc_host, params_dev, params_host, stream=No
                                   params_host.ctypes.data, b, stream if stream is not None else _stream()),
           "dj_ssd_photometric")
     return src
+
+
+# ---- Pascal-VOC evaluation: greedy matching, then cumulative counts / precision / recall / sampled AP -------------------------
+def _check_eval_tensor(t, name, dtype, numel):
+    assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel, \
+        "%s: expected a contiguous %s CUDA tensor of %d elements" % (name, dtype, numel)
+
+
+def eval_match(pred_boxes, seg_ranks, seg_offsets, seg_class, seg_image, class_offsets, gt_boxes, gt_class, gt_neutral,
+               gt_offsets, max_gt_per_image, use_neutral, matching_iou_threshold, border_pixels, tp, fp):
+    """dj_eval_match on the arrays of eval_utils/device_matching.py:pack_evaluation (CUDA tensors of the same dtypes):
+    writes the true / false positive flags of every prediction at class offset + rank into the zeroed int32 tensors
+    `tp` / `fp`.  `border_pixels`: 0 'half', 1 'include', -1 'exclude'."""
+    n_pred, n_seg, n_gt = pred_boxes.shape[0], seg_class.numel(), gt_class.numel()
+    n_classes, n_images = class_offsets.numel() - 2, gt_offsets.numel() - 1
+    for t, name, dtype, numel in ((pred_boxes, "pred_boxes", torch.float32, n_pred * 4), (seg_ranks, "seg_ranks", torch.int32, n_pred),
+                                  (seg_offsets, "seg_offsets", torch.int32, n_seg + 1), (seg_class, "seg_class", torch.int32, n_seg),
+                                  (seg_image, "seg_image", torch.int32, n_seg),
+                                  (class_offsets, "class_offsets", torch.int32, n_classes + 2),
+                                  (gt_boxes, "gt_boxes", torch.float64, n_gt * 4), (gt_class, "gt_class", torch.int32, n_gt),
+                                  (gt_neutral, "gt_neutral", torch.uint8, n_gt), (gt_offsets, "gt_offsets", torch.int32, n_images + 1),
+                                  (tp, "tp", torch.int32, n_pred), (fp, "fp", torch.int32, n_pred)):
+        _check_eval_tensor(t, name, dtype, numel)
+    check(_L().dj_eval_match(ptr(pred_boxes), ptr(seg_ranks), ptr(seg_offsets), ptr(seg_class), ptr(seg_image), n_seg,
+                             ptr(class_offsets), n_classes, n_pred, ptr(gt_boxes), ptr(gt_class), ptr(gt_neutral),
+                             ptr(gt_offsets), n_images, n_gt, int(max_gt_per_image), int(bool(use_neutral)),
+                             float(matching_iou_threshold), int(border_pixels), ptr(tp), ptr(fp), _stream()), "dj_eval_match")
+    return tp, fp
+
+
+def eval_precision_recall_ap(tp, fp, class_offsets, num_gt, thresholds, cum_tp, cum_fp, precision, recall, ap):
+    """dj_eval_precision_recall_ap: from the int32 flags of `eval_match`, per class the running sums (`cum_tp` / `cum_fp`,
+    int32), `precision` / `recall` (float64) per rank and `ap[class]` (float64, n_classes + 1 entries) sampled at the
+    float64 `thresholds`; `num_gt` holds the n_classes + 1 ground-truth counts as float64."""
+    n_pred, n_classes = tp.numel(), class_offsets.numel() - 2
+    for t, name, dtype, numel in ((tp, "tp", torch.int32, n_pred), (fp, "fp", torch.int32, n_pred),
+                                  (class_offsets, "class_offsets", torch.int32, n_classes + 2),
+                                  (num_gt, "num_gt", torch.float64, n_classes + 1),
+                                  (thresholds, "thresholds", torch.float64, thresholds.numel()),
+                                  (cum_tp, "cum_tp", torch.int32, n_pred), (cum_fp, "cum_fp", torch.int32, n_pred),
+                                  (precision, "precision", torch.float64, n_pred), (recall, "recall", torch.float64, n_pred),
+                                  (ap, "ap", torch.float64, n_classes + 1)):
+        _check_eval_tensor(t, name, dtype, numel)
+    check(_L().dj_eval_precision_recall_ap(ptr(tp), ptr(fp), ptr(class_offsets), n_classes, n_pred, ptr(num_gt),
+                                           ptr(thresholds), thresholds.numel(), ptr(cum_tp), ptr(cum_fp), ptr(precision),
+                                           ptr(recall), ptr(ap), _stream()), "dj_eval_precision_recall_ap")
+    return ap

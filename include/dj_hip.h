@@ -120,6 +120,19 @@ int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const float* dy, const float* 
 int dj_conv2d_nhwc_dgrad_bnbwd(const dj_conv2d_desc* d, const float* dy, const float* w, float* dx, const float* z, int ld_z,
                                const float* mean, const float* invstd, const float* scale, const float* shift,
                                float* partial, void* stream);
+/* Input gradient whose epilogue also applies the ReLU mask of the tensor it differentiates:
+ *   dx[m][c] = mask_x[m][c] > 0 ? conv_transpose(dy, w)[m][c] (+ bias[c]) (+ dx[m][c] when beta) : 0
+ * mask_x [batch*in_h*in_w][ld_mask] is the convolution's own forward input x = relu(Add(...)) -- the output of a residual
+ * block (L/models/keras_ssd300_dct_j2d_resnet.py:96-99).  When this launch is the LAST writer of that block's output
+ * gradient, the gradient is masked once, where it is completed: the BatchNormalization backward passes of the block read
+ * it unmasked-mode (mask_mode 0, no read of x) and an identity shortcut shares the buffer.  Exactly the values of
+ * dj_conv2d_nhwc_dgrad(beta) followed by dj_relu_bwd in place.  One K range per tile: DJ_ERR_ARG when the tuning entry of
+ * direction 1 registers a split reduction, for the strided 1x1 scatter form and in the 16-bit arithmetic modes (fp32
+ * tensors only); dj_conv2d_dgrad_relumask_supported() != 0 says beforehand that none of these applies.  Takes the tile
+ * variant of direction 1's tuning entry; geometries outside the branch-free kernels' preconditions run the generic kernel. */
+int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d);
+int dj_conv2d_nhwc_dgrad_relumask(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias, float* dx,
+                                  int beta, const float* mask_x, int ld_mask, void* stream);
 
 /* Residual Add + ReLU evaluated inside the consumer (the first 1x1 conv of the next bottleneck block,
  * L/models/keras_ssd300_dct_j2d_resnet.py:96-99 then :66-68): the conv's input is

@@ -595,8 +595,19 @@ struct DgradBnBwd {   // dj_conv2d_nhwc_dgrad_bnbwd: see include/dj_hip.h
   float* partial;
 };
 
+struct DgradReluMask {   // dj_conv2d_nhwc_dgrad_relumask: see include/dj_hip.h
+  const float* x;
+  int ld;
+};
+
+static inline bool dgrad_is_strided_1x1(const dj_conv2d_desc* d) {
+  return d->kernel_h == 1 && d->kernel_w == 1 && d->pad_top == 0 && d->pad_left == 0 && (d->stride_h > 1 || d->stride_w > 1) &&
+         d->stride_h == d->stride_w;
+}
+
 static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias, float* dx, int beta,
-                           const DgradBnBwd* bnb, void* stream, int dt_dy = DJ_F32, int dt_dx = DJ_F32, int dt_w = DJ_F32) {
+                           const DgradBnBwd* bnb, void* stream, int dt_dy = DJ_F32, int dt_dx = DJ_F32, int dt_w = DJ_F32,
+                           const DgradReluMask* rm = nullptr) {
   if (int rc = check_desc(d)) return rc;
   DJ_CHECK_ARG(dy && w && dx, "conv dgrad: null tensor");
   const bool io16 = dt_dy != DJ_F32 || dt_dx != DJ_F32 || dt_w != DJ_F32 || (bnb && bnb->dt_z != DJ_F32);
@@ -641,10 +652,17 @@ static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float
   p.c_dt = dt_dx;
   const int es_dx = dt_size(dt_dx);
   const long in_pixels = (long)d->batch * d->in_h * d->in_w;
-  bool strided_1x1 = d->kernel_h == 1 && d->kernel_w == 1 && d->pad_top == 0 && d->pad_left == 0 &&
-                     (d->stride_h > 1 || d->stride_w > 1) && d->stride_h == d->stride_w && bias == nullptr;
+  bool strided_1x1 = dgrad_is_strided_1x1(d) && bias == nullptr;
   int splits = 1;
   DJ_CHECK_ARG(!(bnb && strided_1x1), "conv dgrad + BN backward statistics: not for strided 1x1 convolutions");
+  if (rm) {
+    DJ_CHECK_ARG(!bnb && !io16, "conv dgrad + ReLU mask: fp32 tensors, no BN backward statistics");
+    DJ_CHECK_ARG(!dgrad_is_strided_1x1(d), "conv dgrad + ReLU mask: not for strided 1x1 convolutions (their dx is scattered)");
+    const int mode = dj_compute_mode();
+    DJ_CHECK_ARG(mode != 1 && mode != 2, "conv dgrad + ReLU mask: not in the 16-bit arithmetic modes");
+    p.mask_x = rm->x;
+    p.ld_mask = rm->ld;
+  }
   if (strided_1x1) {
     // compact GEMM over the output grid, rows scattered to the strided input pixels
     p.M = d->batch * d->out_h * d->out_w;
@@ -688,7 +706,14 @@ static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float
   int cfg = choose_cfg(p.M, p.N, p.K, true, &splits);
   // the launch that also takes BatchNormalization backward statistics runs the EPI twin and is never split: a tuner
   // entry of its own (direction 9), falling back to the plain input gradient's tile variant
-  if (!(bnb && tune_lookup(9, d, &cfg, &splits))) tune_lookup(1, d, &cfg, &splits);
+  bool tuned1 = false;
+  if (!(bnb && tune_lookup(9, d, &cfg, &splits))) tuned1 = tune_lookup(1, d, &cfg, &splits);
+  if (rm) {
+    // the masked accumulate completes the value in registers: one K range.  A registered split factor is a measured
+    // choice this launch cannot honour -- an error; the launcher's untuned guess is simply not split
+    DJ_CHECK_ARG(!(tuned1 && splits > 1), "conv dgrad + ReLU mask: the tuning entry of this geometry splits the reduction");
+    splits = 1;
+  }
   if (one_k_range || dt_dx != DJ_F32) splits = 1;   // (a 16-bit result is written by one K range: no atomics)
   p.kchunk = dj_cdiv(dj_cdiv(p.K, splits), DJ_BK) * DJ_BK;
   splits = dj_cdiv(p.K, p.kchunk);
@@ -722,6 +747,24 @@ extern "C" int dj_conv2d_nhwc_dgrad_bnbwd(const dj_conv2d_desc* d, const float* 
   DgradBnBwd b{z, DJ_F32, ld_z, mean, invstd, scale, shift, partial};
   // one K range per tile, no accumulation: the accumulator of a tile IS the gradient the statistics are taken of
   return conv_dgrad_impl(d, dy, w, nullptr, dx, DJ_DGRAD_NO_SPLIT, &b, stream);
+}
+
+extern "C" int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d) {
+  if (check_desc(d)) return 0;
+  const int mode = dj_compute_mode();
+  if (mode == 1 || mode == 2 || dgrad_is_strided_1x1(d)) return 0;
+  int cfg = 0, splits = 1;
+  if (tune_lookup(1, d, &cfg, &splits) && splits > 1) return 0;
+  return 1;
+}
+
+extern "C" int dj_conv2d_nhwc_dgrad_relumask(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias,
+                                             float* dx, int beta, const float* mask_x, int ld_mask, void* stream) {
+  DJ_CHECK_ARG(mask_x != nullptr, "conv dgrad + ReLU mask: null mask tensor");
+  DJ_CHECK_ARG(d && ld_mask >= d->in_c, "conv dgrad + ReLU mask: ld_mask < in_c");
+  DJ_CHECK_ARG(d && (long)d->batch * d->in_h * d->in_w * (long)ld_mask < (1L << 31), "conv dgrad + ReLU mask: mask exceeds 2^31 elements");
+  DgradReluMask m{mask_x, ld_mask};
+  return conv_dgrad_impl(d, dy, w, bias, dx, beta & 1, nullptr, stream, DJ_F32, DJ_F32, DJ_F32, &m);
 }
 
 // Input gradient over tensors that carry their storage type: the superset of dj_conv2d_nhwc_dgrad (z == NULL) and

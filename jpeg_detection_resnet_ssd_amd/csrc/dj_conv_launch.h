@@ -55,7 +55,7 @@ static int launch_kernel(KernT kern, int smem_bytes, int bm, int bn, const DjIge
 }
 
 // One launch site per kernel instantiation; an input-gradient launch that asks for BatchNormalization backward statistics
-// (p.bnb_z) takes the EPI = 1 twin of the same variant.
+// (p.bnb_z) takes the EPI = 1 twin of the same variant, one that asks for the masked accumulate (p.mask_x) the EPI = 2 twin.
 template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE, int PREC, int KS, int NP>
 static int launch_fast(int smem_bytes, const DjIgemmParams& p, int splits, hipStream_t s, int threads = 256) {
   if constexpr (AM == 1 && BMD == 1 && PRO == 0) {   // (the input-gradient GEMM has no prologue)
@@ -64,6 +64,15 @@ static int launch_fast(int smem_bytes, const DjIgemmParams& p, int splits, hipSt
       return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 1>, smem_bytes, BM, BN, p,
                            splits, s, &done1, threads);
     }
+    if (p.mask_x) {
+      static std::atomic<bool> done2{false};
+      return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 2>, smem_bytes, BM, BN, p,
+                           splits, s, &done2, threads);
+    }
+  }
+  if (p.mask_x) {
+    dj_set_error("masked accumulate outside the input-gradient GEMM");
+    return DJ_ERR_ARG;
   }
   static std::atomic<bool> done0{false};
   return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 0>, smem_bytes, BM, BN, p, splits,
@@ -114,6 +123,15 @@ static int launch_one(const DjIgemmParams& p, int splits, hipStream_t s, int fas
       return launch_fast<BM, BN, WM, WN, AM, BMD, 3, NSTAGE, 0, 1, 0>(smem_fast, p, splits, s);
     } else {
       dj_set_error("residual-add prologue outside the forward GEMM");
+      return DJ_ERR_ARG;
+    }
+  }
+  if (p.mask_x) {   // masked accumulate on the generic kernel: its EPI = 2 twin (input-gradient GEMM only)
+    if constexpr (AM == 1 && BMD == 1) {
+      static std::atomic<bool> done2{false};
+      return launch_kernel(dj_igemm_kernel<BM, BN, WM, WN, AM, BMD, 2>, Cfg::SMEM_BYTES, BM, BN, p, splits, s, &done2);
+    } else {
+      dj_set_error("masked accumulate outside the input-gradient GEMM");
       return DJ_ERR_ARG;
     }
   }

@@ -4,7 +4,9 @@
 #include "dj_conv_launch.h"
 #include "dj_igemm_h16.h"
 
-// an input-gradient launch that asks for BatchNormalization backward statistics (p.bnb_z) takes the EPI = 1 twin.
+// an input-gradient launch that asks for BatchNormalization backward statistics (p.bnb_z) takes the EPI = 1 twin, one that
+// asks for the masked accumulate (p.mask_x) the EPI = 2 twin -- which exists for the split-bf16 fp32 arithmetic (PREC 3 / 4,
+// fp32 tensors) only: the 16-bit modes do not use it.
 // AT / BT: how the operands A (and A2) / B are stored in HBM (0 fp32, 1 fp16, 2 bf16), see dj_igemm_h16.h.
 template <int BM, int BN, int AM, int BMD, int PRO, int PREC, int BK, int PF, int AT, int BT, int NP>
 static int launch_h16_np(int smem_bytes, const DjIgemmParams& p, int splits, hipStream_t s) {
@@ -14,6 +16,17 @@ static int launch_h16_np(int smem_bytes, const DjIgemmParams& p, int splits, hip
       return launch_kernel(dj_igemm_h16_kernel<BM, BN, AM, BMD, PRO, PREC, BK, PF, 1, AT, BT, NP>, smem_bytes, BM, BN, p, splits,
                            s, &done1, 256);
     }
+    if constexpr (PREC >= 3 && AT == 0 && BT == 0) {
+      if (p.mask_x) {
+        static std::atomic<bool> done2{false};
+        return launch_kernel(dj_igemm_h16_kernel<BM, BN, AM, BMD, PRO, PREC, BK, PF, 2, AT, BT, NP>, smem_bytes, BM, BN, p,
+                             splits, s, &done2, 256);
+      }
+    }
+  }
+  if (p.mask_x) {
+    dj_set_error("masked accumulate: no such kernel for this GEMM role / arithmetic mode");
+    return DJ_ERR_ARG;
   }
   static std::atomic<bool> done0{false};
   return launch_kernel(dj_igemm_h16_kernel<BM, BN, AM, BMD, PRO, PREC, BK, PF, 0, AT, BT, NP>, smem_bytes, BM, BN, p, splits, s,

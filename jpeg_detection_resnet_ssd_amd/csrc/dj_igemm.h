@@ -90,6 +90,11 @@ struct DjIgemmParams {
   // A2) and B select a kernel instantiation, the others are looked at once per tile.  With a 16-bit operand the pointer
   // fields above are reinterpreted; ld* stay in elements, *_bytes are real byte extents.
   int a_dt, b_dt, c_dt, sum_dt, bnb_zdt;
+  // Masked accumulate of the input-gradient GEMM (the EPI = 2 kernels): C = (mask_x > 0) ? acc (+ bias) (+ C) : 0 with mask_x
+  // [M][ld_mask] -- the GEMM's own forward input x = relu(Add): the launch that completes a residual block's output gradient
+  // also applies that block's ReLU mask, so the BatchNormalization backward passes behind it never read x.  null: off
+  const float* mask_x;
+  int ld_mask;             // floats between consecutive rows of mask_x
 };
 
 template <int BM, int BN, int WM, int WN, int AM, int BMD>
@@ -227,6 +232,44 @@ __device__ __forceinline__ void dj_store_full_tile(float* ubase, unsigned lane_b
 #pragma unroll
           for (int j = 0; j < TN; ++j) *reinterpret_cast<float*>(rowb + q * row_bytes + j * 128 + lane_byte) = v[q][j];
       }
+      __builtin_amdgcn_sched_barrier(0);   // one group's values live at a time
+    }
+}
+
+// Twin of dj_store_full_tile for the masked accumulate (DjIgemmParams::mask_x): v = acc + bias (+ C), stored as
+// (mask > 0) ? v : 0.  A loop of its own, compiled into the EPI = 2 kernels only: the shared loop above stays as it is
+// (see its comment for what a further flag in it costs).  The mask loads of a four-row group are issued with the group's C
+// loads, so one group's values are live at a time as before.  umask / lane_mbyte address the mask like ubase / lane_byte.
+template <int TM, int TN>
+__device__ __forceinline__ void dj_store_full_tile_relumask(float* ubase, unsigned lane_byte, const float* umask,
+                                                            unsigned lane_mbyte, const f32x16 (&acc)[TM][TN],
+                                                            const float (&bv)[TN], int ldc, int ldm, bool beta) {
+  const size_t row_bytes = (size_t)ldc * 4, mrow_bytes = (size_t)ldm * 4;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float v[4][TN], mk[4][TN];
+      char* rowb = reinterpret_cast<char*>(ubase) + (size_t)(i * 32 + 8 * g) * row_bytes;
+      const char* mrowb = reinterpret_cast<const char*>(umask) + (size_t)(i * 32 + 8 * g) * mrow_bytes;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          v[q][j] = acc[i][j][4 * g + q] + bv[j];
+          mk[q][j] = *reinterpret_cast<const float*>(mrowb + q * mrow_bytes + j * 128 + lane_mbyte);
+        }
+      if (beta) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) v[q][j] += *reinterpret_cast<const float*>(rowb + q * row_bytes + j * 128 + lane_byte);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          *reinterpret_cast<float*>(rowb + q * row_bytes + j * 128 + lane_byte) = (mk[q][j] > 0.f) ? v[q][j] : 0.f;
       __builtin_amdgcn_sched_barrier(0);   // one group's values live at a time
     }
 }
@@ -399,7 +442,10 @@ __device__ __forceinline__ void dj_store_tile16_via_lds(short* wave_lds, char* u
 // (128x128 forward variants 160 -> 180 VGPRs, i.e. three waves per SIMD -> two; the residual-add variants 26-42 SGPR spills)
 // IO16: the kernel may be handed 16-bit tensors (c_dt / bnb_zdt: the reduced-precision kernels of dj_igemm_h16.h only)
 // LDSB: bytes of dynamic LDS the kernel owns (0: unknown -- no LDS-staged stores)
-template <int BM, int BN, int WM, int WN, bool BNB = false, bool IO16 = false, int LDSB = 0>
+// RMASK: the masked accumulate of the input-gradient GEMM (DjIgemmParams::mask_x, fp32 C, plain row map, one K range, no
+//   statistics): the stores below are replaced by dj_store_full_tile_relumask and an edge loop of its own.  A template
+//   parameter, not a run-time test, so that the kernels that are not asked for it keep their code and registers.
+template <int BM, int BN, int WM, int WN, bool BNB = false, bool IO16 = false, int LDSB = 0, bool RMASK = false>
 __device__ __forceinline__ void dj_igemm_epilogue(const DjIgemmParams& p, f32x16 (&acc)[BM / (32 * WM)][BN / (32 * WN)],
                                                   float* smem, int tile_m, int m0, int n0, int ky) {
   constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
@@ -407,7 +453,7 @@ __device__ __forceinline__ void dj_igemm_epilogue(const DjIgemmParams& p, f32x16
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, lh = lane >> 5;
-  if (p.stats || p.bn_acc) {
+  if (!RMASK && (p.stats || p.bn_acc)) {
     // per-column sum and sum of squares of the raw accumulator over this tile's rows
     float* red = smem;  // [2][WM][BN]
 #pragma unroll
@@ -515,6 +561,40 @@ __device__ __forceinline__ void dj_igemm_epilogue(const DjIgemmParams& p, f32x16
     }
   }
 
+  if constexpr (RMASK) {
+    if (m0 + BM <= p.M && n0 + BN <= p.N) {
+      float bv[TN];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bv[j] = p.bias ? p.bias[n0 + (wn * TN + j) * 32 + l31] : 0.f;
+      const int uwave = __builtin_amdgcn_readfirstlane(wave);
+      const int uwm = uwave / WN, uwn = uwave % WN;
+      float* ubase = p.C + (size_t)(m0 + uwm * TM * 32) * p.ldc + (n0 + uwn * TN * 32);
+      const float* umask = p.mask_x + (size_t)(m0 + uwm * TM * 32) * p.ld_mask + (n0 + uwn * TN * 32);
+      const unsigned lane_byte = (unsigned)(4 * lh * p.ldc + l31) * 4u, lane_mbyte = (unsigned)(4 * lh * p.ld_mask + l31) * 4u;
+      dj_store_full_tile_relumask<TM, TN>(ubase, lane_byte, umask, lane_mbyte, acc, bv, p.ldc, p.ld_mask, p.beta != 0);
+    } else {
+      // tiles that hang over M or N: per-element tests, as in the general loop below
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          if (m >= p.M) continue;
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wn * TN + j) * 32 + l31;
+            if (n >= p.N) continue;
+            float v = acc[i][j][r];
+            float* dst = p.C + (size_t)m * p.ldc + n;
+            if (p.bias) v += p.bias[n];
+            if (p.beta) v += *dst;
+            *dst = (p.mask_x[(size_t)m * p.ld_mask + n] > 0.f) ? v : 0.f;
+          }
+        }
+      }
+    }
+    return;
+  }
   float* const Cb = p.C + (size_t)ky * p.slab_stride;   // ky: this workgroup's K chunk
   if (IO16) {
     // the reduced-precision kernels: C in fp32 (possibly atomic / slabs) or in 16 bits (one K range, never atomic)
@@ -675,8 +755,10 @@ __device__ __forceinline__ void dj_igemm_epilogue(const DjIgemmParams& p, f32x16
   }
 }
 
-template <int BM, int BN, int WM, int WN, int AM, int BMD>
+// EPI: 2 = the masked accumulate of the input-gradient GEMM (DjIgemmParams::mask_x), see dj_igemm_fast.h
+template <int BM, int BN, int WM, int WN, int AM, int BMD, int EPI = 0>
 __global__ __launch_bounds__(256) void dj_igemm_kernel(const DjIgemmParams p) {
+  static_assert(EPI == 0 || (EPI == 2 && AM == 1 && BMD == 1), "masked accumulate: input-gradient GEMM only");
   using Cfg = DjIgemmCfg<BM, BN, WM, WN, AM, BMD>;
   constexpr int TM = Cfg::TM, TN = Cfg::TN, NA = Cfg::NA, NB = Cfg::NB;
   constexpr int LDA_S = Cfg::LDA_S, LDB_S = Cfg::LDB_S;
@@ -1010,5 +1092,5 @@ __global__ __launch_bounds__(256) void dj_igemm_kernel(const DjIgemmParams p) {
     buf ^= 1;
   }
 
-  dj_igemm_epilogue<BM, BN, WM, WN, (AM == 1 && BMD == 1)>(p, acc, smem, tile_m, m0, n0, (int)blockIdx.y);
+  dj_igemm_epilogue<BM, BN, WM, WN, (AM == 1 && BMD == 1), false, 0, EPI == 2>(p, acc, smem, tile_m, m0, n0, (int)blockIdx.y);
 }

@@ -153,6 +153,7 @@ __device__ __forceinline__ void dj_split_store3(short* dst, f32x4 v, int lo_off)
 // step earlier) goes to LDS: a load has a full K-step longer to land (small tiles, whose steps are short; costs one
 // more set of staging registers).
 // EPI: 1 = the epilogue also takes BatchNormalization backward statistics (see dj_igemm_fast.h), input gradient only.
+//      2 = the masked accumulate (DjIgemmParams::mask_x, see dj_igemm_fast.h): fp32 tensors, input gradient only.
 // AT, BT: storage type of A (and A2) / of B in HBM, see the header comment.
 // NP: 1 = the gathered operand can never leave its tensor (1x1 kernel, no padding; for the weight gradient also stride 1,
 //     input pixel == output pixel): the K-step has no coordinate adds, bounds tests or offset selects -- a row's validity is
@@ -164,6 +165,7 @@ template <int BM, int BN, int AM, int BMD, int PRO, int PREC, int BK = 32, int P
 __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p) {
   static_assert(NP == 0 || PRO != 3, "NP: not with the residual-add prologue (which keeps row indices of its own)");
   static_assert(EPI == 0 || (AM == 1 && BMD == 1), "BatchNormalization backward statistics: input-gradient GEMM only");
+  static_assert(EPI != 2 || (PRO == 0 && AT == 0 && BT == 0), "masked accumulate: fp32 tensors, no prologue");
   static_assert(PREC < 3 || (AT == 0 && BT == 0), "float32x3 / float32x6: fp32 tensors");
   constexpr int EA = AT ? 2 : 4, EB = BT ? 2 : 4;   // bytes per stored element
   using ARaw = typename DjRaw<AT>::type;
@@ -621,5 +623,5 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
     kstep(First{}, r0, r0, 0, kbeg + BK, 1 < nk);
     for (int kt = 1; kt < nk; ++kt) kstep(Later{}, r0, r0, kt, kbeg + (kt + 1) * BK, kt + 1 < nk);
   }
-  dj_igemm_epilogue<BM, BN, 2, 2, EPI == 1, true, Cfg::SMEM_BYTES * IMGS>(p, acc, smem_base, tile_m, m0, n0, ky);
+  dj_igemm_epilogue<BM, BN, 2, 2, EPI == 1, true, Cfg::SMEM_BYTES * IMGS, EPI == 2>(p, acc, smem_base, tile_m, m0, n0, ky);
 }

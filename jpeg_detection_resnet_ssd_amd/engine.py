@@ -252,6 +252,14 @@ class GradRef(object):
         self.also = also
         # (partial rows, count): the BatchNormalization backward statistics of this gradient, taken by the GEMM that wrote it
         self.bwd_partial = None
+        # True: the buffer already holds the gradient masked by its Value's own ReLU -- its last writer was an input-gradient
+        # GEMM with the mask in its epilogue (kernels.conv2d_dgrad(relu_mask=...)); nobody may accumulate into it any more
+        self.premasked = False
+        # set by a reader (BatchNormalization backward) once its launches that read `buf` are in the backward list
+        self.consumed = False
+        # this reference shares its buffer with an earlier gradient (identity shortcut behind a pre-masked block output):
+        # the GradRefs through which that earlier gradient is still read; all must be `consumed` before the first write here
+        self.alias_readers = ()
 
 
 class Value(object):
@@ -346,6 +354,7 @@ class Plan(object):
         self.deferred_colsums = []   # (dy, rows, c, ld, grad buffer, weight spec): see build_backward
         self.conv_calls = []   # (direction, ConvDesc, launch closure) of every implicit-GEMM call, for autotune()
         self.fused_outputs = {}   # id(Conv2D layer) -> Value, for layers lowered inside a sibling's fused GEMM
+        self.masked_dgrads = []   # names of the Conv2D layers whose input gradient applies the ReLU mask of a block output
         # the arithmetic mode this plan was lowered under (K.set_floatx at that time): its launches run in it whatever the
         # process default or another plan's mode is by then (per-thread override of the C library)
         self.compute_mode = int(_lib.load().dj_get_compute_mode()) if device.type == "cuda" else 0
@@ -572,6 +581,8 @@ class Plan(object):
         names = [n for n, _ in _lib.ConvDesc._fields_][:15]
         done = 0
         grown = False
+        # geometries one of whose launches cannot be split over K (masked accumulate): their shared entry stays unsplit
+        unsplit = {(d,) + tuple(getattr(ds, n) for n in names) for d, ds, f in self.conv_calls if getattr(f, "no_split", False)}
         for direction, desc, fn in self.conv_calls:
             key = (direction,) + tuple(getattr(desc, n) for n in names)
             if key in _TUNED:
@@ -594,7 +605,7 @@ class Plan(object):
             c0, s0 = ctypes.c_int(0), ctypes.c_int(1)
             check(lib.dj_conv2d_default_config(direction, desc, ctypes.byref(c0), ctypes.byref(s0)), "default_config")
             base = direction & 3
-            if direction & 4 or direction == 9 or getattr(fn, "no_split", False):
+            if direction & 4 or direction == 9 or key in unsplit:
                 split_opts = [1]
             elif base == 2:
                 kk = desc.batch * desc.out_h * desc.out_w
@@ -681,7 +692,21 @@ class Plan(object):
             v.grad = GradRef(self.empty(*v.buf.shape, dtype=gdt))
             return v.grad.buf, 0
         assert v.grad.mask_y is None, "cannot accumulate into a masked gradient reference"
+        assert not v.grad.premasked, "gradient of %s was masked by its last writer and gets another one" % v.name
+        # a buffer shared with the gradient of the next block output is overwritten in place from here on: every launch
+        # that reads it as that gradient must already be in the list (they all run on the main stream, in list order; the
+        # side stream's weight gradients read BatchNormalization's dz, never this buffer)
+        assert all(r.consumed for r in v.grad.alias_readers), \
+            "the gradient buffer %s shares would be overwritten before a reader of its previous contents is emitted" % v.name
         return v.grad.buf, 1
+
+    def alias_grad(self, v, buf, readers):
+        """Make the (so far unwritten) gradient of `v` live in `buf`, which holds a gradient that IS the first contribution
+        to it (identity shortcut: d relu(Add) / d shortcut = the masked upstream gradient, no copy); later writers accumulate
+        in place.  `readers`: GradRefs through which the present contents are still to be read (see grad_of)."""
+        assert v.alias_of is None and v.grad is None and tuple(buf.shape) == tuple(v.buf.shape)
+        v.grad = GradRef(buf)
+        v.grad.alias_readers = readers
 
     def set_grad_ref(self, v, ref):
         assert v.alias_of is None and v.grad is None, "gradient of %s already has a writer" % v.name

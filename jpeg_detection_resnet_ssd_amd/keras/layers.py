@@ -269,6 +269,27 @@ def _bn_backward_fusable(plan, model, layer, x):
     return bnv
 
 
+def _relu_mask_in_dgrad(plan, layer, x, desc, dy, w_bwd, own_memset):
+    """-> the tensor whose sign the input-gradient GEMM of `layer` applies in its epilogue (kernels.conv2d_dgrad_relumask),
+    or None.  `x` = relu(Add(...)) is a residual block's output and `layer` its first consumer in layer order, i.e. the LAST
+    writer of x's gradient: the launch that completes that gradient masks it, the BatchNormalization backward passes of the
+    block run in mask_mode 0 and never read x, and an identity shortcut shares the buffer (Add.build_backward).  Per element
+    of a block output the chain moves 32 bytes instead of 40.  DJ_MASK_IN_DGRAD=0/1 switches it (A/B runs); not for stage
+    ends whose gradient has later writers, split-K or strided input gradients, or 16-bit tensors."""
+    if os.environ.get("DJ_MASK_IN_DGRAD", _MASK_IN_DGRAD_DEFAULT) == "0" or not plan.training:
+        return None
+    if getattr(x, "add_relu_first", None) is not layer or x.alias_of is not None or x.pad is not None or x.is_affine:
+        return None
+    if own_memset or plan.store16 or plan.compute_mode in (1, 2):
+        return None
+    if any(t.dtype != torch.float32 for t in (x.buf, dy, w_bwd)):
+        return None
+    return x.buf if Kn.conv2d_dgrad_relumask_supported(desc) else None
+
+
+_MASK_IN_DGRAD_DEFAULT = "1"
+
+
 class Conv2D(Layer):
     """keras.layers.Conv2D(filters, kernel_size, strides=(1,1), padding='valid', dilation_rate=(1,1),
     activation=None, use_bias=True, kernel_initializer='glorot_uniform', kernel_regularizer=None)."""
@@ -570,8 +591,17 @@ class Conv2D(Layer):
                     plan.emit_conv(9, desc, fused_dgrad, backward=True)   # tuned and recorded apart from plain dgrads
                     x.grad.bwd_partial = (part, nr)
                 else:
+                    mask = _relu_mask_in_dgrad(plan, self, x, desc, dy, w_bwd, own_memset)
                     dx, beta = plan.grad_of(x, zeroed=own_memset and os.environ.get("DJ_ZERO_ARENA", "1") != "0")
-                    plan.emit_conv(1, desc, Kn.bound("conv2d_dgrad", desc, dy, w_bwd, dx, None, bool(beta)), backward=True)
+                    if mask is not None:
+                        # last writer of a block output's gradient: complete it and apply the block's ReLU mask in one go
+                        masked_dgrad = Kn.bound("conv2d_dgrad_relumask", desc, dy, w_bwd, dx, mask, None, bool(beta))
+                        masked_dgrad.no_split = True     # for the tuners: the masked accumulate has one K range
+                        plan.emit_conv(1, desc, masked_dgrad, backward=True)
+                        x.grad.premasked = True
+                        plan.masked_dgrads.append(self.name)
+                    else:
+                        plan.emit_conv(1, desc, Kn.bound("conv2d_dgrad", desc, dy, w_bwd, dx, None, bool(beta)), backward=True)
 
         plan.on_backward(build_backward)
         return out
@@ -834,6 +864,7 @@ class BatchNormalization(Layer):
             elif also is not None:   # nothing to apply here: the shortcut still needs its masked gradient
                 dm, dm_beta = also
                 plan.emit_bwd(launcher(*Kn.relu_bwd_call(dy, ld_dy, mask_y, ld_y, dm, rows_of(dm)[2], rows, c, int(dm_beta))))
+            src.grad.consumed = True     # every launch of this layer that reads dy is in the list
 
         plan.on_backward(build_backward)
         return out
@@ -924,6 +955,7 @@ class Add(Layer):
         abuf, bbuf = a.buf, b.buf
         out = Value(y, needs_grad=a.needs_grad or b.needs_grad, name=self.name)
         first = self._first_consumer_conv(plan, model, consumers[0] if relu else None, a, y, b) if relu else None
+        out.add_relu_first = first      # the layer whose input gradient is the last writer of this sum's gradient
         if first is not None:
             # no launch here: `first` (the next block's 1x1 conv) computes relu(bn(a) + b) in its A-tile prologue and
             # stores it to y (dj_conv2d_nhwc_fwd_addrelu) -- one elementwise pass and one read of y less per block
@@ -938,21 +970,35 @@ class Add(Layer):
                 return
             assert out.grad.mask_y is None
             dy = out.grad.buf
+            # pre-masked: the input-gradient GEMM that completed dy applied this ReLU's mask already (Conv2D.build_backward,
+            # _relu_mask_in_dgrad): the branches take dy as it is -- BatchNormalization backward in mask_mode 0, no read of y
+            premasked = out.grad.premasked
+            assert relu or not premasked
+            relu_here = relu and not premasked
             # identity block: the BatchNormalization branch applies the ReLU mask anyway (dj_bn_bwd_apply); it writes the
             # masked gradient for the identity shortcut in the same pass instead of a separate dj_relu_bwd sweep
-            fuse = (relu and a.is_affine and a.needs_grad and not b.is_affine and b.needs_grad
+            fuse = (relu_here and a.is_affine and a.needs_grad and not b.is_affine and b.needs_grad
                     and getattr(a, "bn_applies_mask", False))
+            readers, shared = [], False
             for v in (a, b):
                 if not v.needs_grad:
                     continue
                 if v.is_affine:
                     also = plan.grad_of(b) if (fuse and v is a) else None
-                    plan.set_grad_ref(v, GradRef(dy, y if relu else None, also=also))
+                    plan.set_grad_ref(v, GradRef(dy, y if relu_here else None, also=also))
+                    readers.append(v.grad)
                 elif fuse:
                     continue
+                elif (premasked and not shared and v.grad is None and v.alias_of is None and v.buf.shape == dy.shape
+                      and plan.grad_dtype(v.buf) == dy.dtype and dy.is_contiguous()):
+                    # identity shortcut behind a pre-masked sum: its gradient IS dy.  No copy (the `dmasked` store of
+                    # dj_bn_bwd_apply): the shortcut's gradient lives in dy's buffer and its remaining writers -- the first
+                    # conv of this block -- accumulate in place, once the BatchNormalization branch has read dy
+                    plan.alias_grad(v, dy, readers)
+                    shared = True
                 else:
                     dv, beta = plan.grad_of(v)
-                    if relu:
+                    if relu_here:
                         bw = Kn.relu_bwd_call(dy, c, y, c, dv, rows_of(dv)[2], rows, c, beta)
                     else:
                         bw = Kn.copy2d_call(dy, c, dv, rows_of(dv)[2], rows, c, beta)

@@ -4,7 +4,9 @@ localisation_part/evaluation.py (same positional `weights`, `--archi`, dataset f
 model family built here), `mode='inference'` model with the on-device DecodeDetections layer, `Evaluator(...)` with the
 reference's settings (evaluation.py:102-131: batch 8, 'resize', 11-point sampling, IoU 0.5, 'include' borders).
 Matching, precision / recall and AP run on the GPU (csrc/dj_eval.hip, results equal bit for bit to the host loop, equal
-confidences ranked in list order); `--host_matching` restores the host loop.
+confidences ranked in list order), and the detections stay on the GPU from the DecodeDetections layer to the matching
+(csrc/dj_eval_collect.hip); `--host_matching` restores the whole host path, `--host_predictions` only the host's collection
+of the detections into python lists.
 The VOC XML/JPEG dataset readers are out of scope; `--generator module:factory` plugs one in, the default is
 the synthetic JPEG-DCT dataset."""
 import importlib
@@ -31,6 +33,8 @@ parser.add_argument("--synthetic_images", type=int, default=64)
 parser.add_argument("--batch_size", type=int, default=8)
 parser.add_argument("--host_matching", action="store_true", default=False,
                     help="match predictions and compute precision / recall / AP with the host numpy loop instead of the GPU")
+parser.add_argument("--host_predictions", action="store_true", default=False,
+                    help="download every decoded batch and collect the detections in python lists instead of on the GPU")
 args = parser.parse_args()
 if args.ssd or args.ssd_other or args.ssd_dct or args.ssd_miisst or args.ssd_miisst_dct:
     raise SystemExit("only the ResNet50-DCT SSD family (-r, --archi ...) is built here; the VGG models are out of scope")
@@ -73,7 +77,8 @@ if args.archi == "deconv":
 classes = ["background", "aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow",
            "diningtable", "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor"]
 evaluator = Evaluator(model=model, n_classes=n_classes, data_generator=dataset, model_mode=model_mode,
-                      device_matching=not args.host_matching)
+                      device_matching=not args.host_matching,
+                      device_predictions=not (args.host_matching or args.host_predictions))
 results = evaluator(img_height=img_height, img_width=img_width, batch_size=args.batch_size, data_generator_mode="resize",
                     round_confidences=False, matching_iou_threshold=0.5, border_pixels="include",
                     sorting_algorithm="quicksort", average_precision_mode="sample", num_recall_points=11,

@@ -581,6 +581,47 @@ int dj_eval_precision_recall_ap(const int* tp, const int* fp, const int* class_o
                                 const double* num_gt, const double* thresholds, int num_recall_points, int* cum_tp,
                                 int* cum_fp, double* precision, double* recall, double* ap, void* stream);
 
+/* ---- The stages in front of dj_eval_match (L/eval_utils/average_precision_evaluator.py:262-470, the loop of
+ * `predict_on_dataset`, and the prediction half of device_matching.py:pack_evaluation), equal bit for bit to the host and
+ * stated in numpy by device_matching.py:collect_host / rank_host.  Device pointers unless said otherwise; neither entry
+ * point synchronises with the host.  counters [4] int32, zeroed by the caller once per evaluation: [0] records appended,
+ * [1] errors (a class id that is no integer in 1..n_classes, a NaN confidence), [2] segments, [3] records dropped for lack
+ * of room (the host-side capacity check keeps it 0).
+ * dj_eval_collect: decoded [batch][rows][6] float32 = (class id, conf, xmin, ymin, xmax, ymax) as DecodeDetections leaves
+ * it, rows with class id 0 are padding (anywhere among the rows).  Of the first n_valid images every other row is appended
+ * behind counters[0], image after image and rows in their order, to the record arrays of `capacity` entries: rec_class,
+ * rec_image (desc.image_index), rec_ordinal (first_ordinal + the image's place in the batch: which collected image the row
+ * came from), rec_conf float32, rec_conf64 (the same before its conversion to float32), rec_boxes [capacity][4] float32.
+ * desc_host [batch] lives on the HOST and travels in the kernel arguments (one launch per 128 images).  kind 1 is the
+ * inverse of `Resize`: y = rintf(y * scale_y), x = rintf(x * scale_x) in float32, the product rounded before rintf; kind
+ * 0 leaves the box alone.  Then every coordinate becomes (float)(rint(10.0 * v) / 10.0) in float64, CPython's
+ * round(float(v), 1), and with conf_digits d in 1..8 the confidence rint(10^d * conf) / 10^d (conf_digits 0: unchanged).
+ * boxes_final != 0: the boxes are stored as they are (the host applied the transforms and the rounding); the confidence
+ * is treated as always.  Refused unless (first_ordinal + n_valid) * rows <= capacity, which bounds counters[0]; the kernel
+ * itself never writes past capacity.
+ * dj_eval_rank: the counters[0] records -> class_offsets [n_classes + 2], pred_class / pred_image / pred_conf / pred_boxes
+ * (class after class, within a class confidence descending with -0.0 == 0.0 and equal confidences in record order),
+ * seg_class / seg_image / seg_offsets [capacity + 1] / seg_ranks as dj_eval_match reads them, segments ordered by
+ * (class, image); counters[2] receives their number.  Every per-prediction array has `capacity` entries, of which the first
+ * counters[0] are written.  workspace: dj_eval_rank_workspace_bytes(capacity, n_classes) bytes, 8-byte aligned.  Sorting is
+ * done here (tiles of 1024 keys in LDS, then merge passes), on unique 64-bit keys, so the result does not depend on the
+ * run. ---- */
+typedef struct {
+  int image_index;     /* position of the image's id in data_generator.image_ids */
+  int kind;            /* 0 identity, 1 resize */
+  float scale_y;       /* img_height / out_height rounded to float32 */
+  float scale_x;       /* img_width / out_width rounded to float32 */
+} dj_eval_collect_desc;
+int dj_eval_collect(const float* decoded, int batch, int rows, int n_valid, const dj_eval_collect_desc* desc_host,
+                    int first_ordinal, int n_classes, int n_images, int conf_digits, int boxes_final, int* rec_class,
+                    int* rec_image, int* rec_ordinal, float* rec_conf, double* rec_conf64, float* rec_boxes, long capacity,
+                    int* counters, void* stream);
+long dj_eval_rank_workspace_bytes(long capacity, int n_classes);
+int dj_eval_rank(const int* rec_class, const int* rec_image, const float* rec_conf, const float* rec_boxes, long capacity,
+                 int n_classes, int n_images, int* counters, int* class_offsets, int* pred_class, int* pred_image,
+                 float* pred_conf, float* pred_boxes, int* seg_class, int* seg_image, int* seg_offsets, int* seg_ranks,
+                 void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

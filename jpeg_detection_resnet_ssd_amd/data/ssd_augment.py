@@ -329,6 +329,10 @@ def _identity_inverter(labels):
     return labels
 
 
+# `device_form`: what an inverter computes, for eval_utils/device_matching.py to run it on the GPU (dj_eval_collect)
+_identity_inverter.device_form = ("identity",)
+
+
 class CropPad(_Plannable):
     """Takes the patch (patch_ymin, patch_xmin, patch_height, patch_width), given in the image's coordinates, out of the
     image: cropped where the patch lies inside, padded with `background` where it does not."""
@@ -523,6 +527,9 @@ class Resize(_Plannable):
             labels[:, [ymin + 1, ymax + 1]] = np.round(labels[:, [ymin + 1, ymax + 1]] * (img_height / self.out_height), decimals=0)
             labels[:, [xmin + 1, xmax + 1]] = np.round(labels[:, [xmin + 1, xmax + 1]] * (img_width / self.out_width), decimals=0)
             return labels
+
+        if (xmin, ymin, xmax, ymax) == (1, 2, 3, 4):     # the columns the device form is stated for
+            inverter.device_form = ("resize", img_height / self.out_height, img_width / self.out_width)
 
         if labels is not None:
             labels = np.copy(labels)

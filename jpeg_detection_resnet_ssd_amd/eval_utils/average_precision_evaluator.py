@@ -10,7 +10,10 @@ difference: the reference iterates `range(len(predictions.shape))` (= 1 predicti
 (:699); here every prediction is matched regardless of `verbose`.
 
 `Evaluator(device_matching=True)` computes the matching, precision / recall and sampled AP on the GPU instead
-(device_matching.py, csrc/dj_eval.hip); the host methods below are the statement those results are equal to."""
+(device_matching.py, csrc/dj_eval.hip); the host methods below are the statement those results are equal to.
+`Evaluator(device_predictions=True)` also keeps the detections on the GPU from the DecodeDetections layer to the matching
+(csrc/dj_eval_collect.hip): `predict_on_dataset` appends every decoded batch to record arrays on the device, and
+`prediction_results` is built from one download when somebody reads it."""
 from math import ceil
 
 import numpy as np
@@ -23,7 +26,7 @@ class Evaluator(object):
     def __init__(self, model, n_classes, data_generator, model_mode="inference",
                  pred_format={"class_id": 0, "conf": 1, "xmin": 2, "ymin": 3, "xmax": 4, "ymax": 5},
                  gt_format={"class_id": 0, "xmin": 1, "ymin": 2, "xmax": 3, "ymax": 4}, ignore_under_area=0,
-                 device_matching=False):
+                 device_matching=False, device_predictions=False):
         self.model = model
         self.data_generator = data_generator
         self.n_classes = n_classes
@@ -33,8 +36,19 @@ class Evaluator(object):
         self.ignore_under_area = ignore_under_area
         # True: match_predictions, compute_precision_recall and compute_average_precisions run on the GPU
         # (eval_utils/device_matching.py, csrc/dj_eval.hip) and leave the same values in the same attributes
-        self.device_matching = device_matching
+        # True (implies device_matching): predict_on_dataset leaves the decoded batches on the GPU and collects them there,
+        # match_predictions ranks and segments them there; `prediction_results` is materialised when it is read
+        self.device_predictions = bool(device_predictions)
+        if self.device_predictions:
+            if model_mode not in ("inference", "inference_fast"):
+                raise ValueError("`device_predictions` needs a model of mode 'inference' or 'inference_fast': in "
+                                 "model_mode='{}' the detections are decoded by the host's numpy".format(model_mode))
+            if [pred_format.get(k) for k in ("class_id", "conf", "xmin", "ymin", "xmax", "ymax")] != list(range(6)):
+                raise ValueError("`device_predictions` reads the layout (class_id, conf, xmin, ymin, xmax, ymax) of the "
+                                 "DecodeDetections layer, not `pred_format` = {}".format(pred_format))
+        self.device_matching = bool(device_matching or self.device_predictions)
         self._device_eval = None
+        self._collector = None
         self.prediction_results = None
         self.num_gt_per_class = None
         self.true_positives = None
@@ -79,6 +93,23 @@ class Evaluator(object):
         return mean_average_precision
 
     # ---- predictions --------------------------------------------------------------------------------------------
+    @property
+    def prediction_results(self):
+        """results[class_id] = list of (image_id, confidence, xmin, ymin, xmax, ymax).  After a `predict_on_dataset` with
+        `device_predictions` the lists are built from one download on the first read; assigning to the attribute puts the
+        evaluator back on the lists."""
+        if self._collector is not None and self._prediction_results is None:
+            self._prediction_results = self._collector.prediction_results()
+        return self._prediction_results
+
+    @prediction_results.setter
+    def prediction_results(self, value):
+        self._prediction_results = value
+        self._collector = None
+
+    def _have_predictions(self):
+        return self._collector is not None or self._prediction_results is not None
+
     def predict_on_dataset(self, img_height, img_width, batch_size, data_generator_mode="resize",
                            decoding_confidence_thresh=0.01, decoding_iou_threshold=0.45, decoding_top_k=200,
                            decoding_pred_coords="centroids", decoding_normalize_coords=True,
@@ -94,6 +125,8 @@ class Evaluator(object):
                                                  keep_images_without_gt=True, degenerate_box_handling="remove")
         if self.data_generator.image_ids is None:
             self.data_generator.image_ids = list(range(self.data_generator.get_dataset_size()))
+        if self.device_predictions:
+            return self._predict_on_dataset_device(generator, batch_size, round_confidences, verbose, ret)
         results = [list() for _ in range(self.n_classes + 1)]
         n_images = self.data_generator.get_dataset_size()
         n_batches = int(ceil(n_images / batch_size))
@@ -112,23 +145,35 @@ class Evaluator(object):
             else:
                 y_pred = [y_pred[i][y_pred[i, :, 0] != 0] for i in range(len(y_pred))]   # drop the zero padding
             y_pred = apply_inverse_transforms(y_pred, batch_inverse_transforms)
-            for k, batch_item in enumerate(y_pred):
-                if seen + k >= n_images:            # the last batch wraps around the dataset
-                    break
-                image_id = batch_image_ids[k]
-                for box in np.asarray(batch_item).reshape(-1, 6):
-                    conf = round(float(box[p["conf"]]), round_confidences) if round_confidences else box[p["conf"]]
-                    results[int(box[p["class_id"]])].append(
-                        (image_id, conf, round(float(box[p["xmin"]]), 1), round(float(box[p["ymin"]]), 1),
-                         round(float(box[p["xmax"]]), 1), round(float(box[p["ymax"]]), 1)))
+            append_batch_results(results, y_pred, batch_image_ids, seen, n_images, round_confidences, p)
             seen += len(y_pred)
         self.prediction_results = results
         if ret:
             return results
 
+    def _predict_on_dataset_device(self, generator, batch_size, round_confidences, verbose, ret):
+        """The loop above with the decoded batches left on the GPU: one forward pass and one dj_eval_collect launch per
+        batch, no download."""
+        from .device_matching import DeviceCollector, conf_digits_of
+        n_images = self.data_generator.get_dataset_size()
+        if verbose:
+            print("Number of images in the evaluation dataset: {}".format(n_images))
+        collector = DeviceCollector(self.n_classes, self.data_generator.image_ids, conf_digits_of(round_confidences))
+        seen = 0
+        for _ in range(int(ceil(n_images / batch_size))):
+            batch_X, batch_image_ids, batch_inverse_transforms = next(generator)
+            decoded = self.model.predict_on_batch(batch_X, to_host=False)
+            n_valid = max(0, min(len(decoded), n_images - seen))        # the last batch wraps around the dataset
+            collector.add(decoded, n_valid, batch_image_ids, batch_inverse_transforms)
+            seen += len(decoded)
+        self._prediction_results = None
+        self._collector = collector
+        if ret:
+            return self.prediction_results
+
     def write_predictions_to_txt(self, classes=None, out_file_prefix="comp3_det_test_", verbose=True):
         """One Pascal-VOC results file per class: `image_id confidence xmin ymin xmax ymax` rows."""
-        if self.prediction_results is None:
+        if not self._have_predictions():
             raise ValueError("There are no prediction results. You must run `predict_on_dataset()` before calling this method.")
         for class_id in range(1, self.n_classes + 1):
             suffix = "{:04d}".format(class_id) if classes is None else classes[class_id]
@@ -173,7 +218,7 @@ class Evaluator(object):
                           sorting_algorithm="quicksort", verbose=True, ret=False):
         if self.data_generator.labels is None:
             raise ValueError("Matching predictions to ground truth boxes not possible, no ground truth given.")
-        if self.prediction_results is None:
+        if not self._have_predictions():
             raise ValueError("There are no prediction results. You must run `predict_on_dataset()` before calling this method.")
         if self.device_matching:
             return self._match_predictions_device(ignore_neutral_boxes, matching_iou_threshold, border_pixels, verbose, ret)
@@ -291,15 +336,22 @@ class Evaluator(object):
     def _match_predictions_device(self, ignore_neutral_boxes, matching_iou_threshold, border_pixels, verbose, ret):
         """`match_predictions` on the GPU.  The rank order is device_matching.pack_evaluation's: confidence descending,
         equal confidences in list order ("mergesort"), whatever `sorting_algorithm` says."""
-        from .device_matching import DeviceEvaluation, pack_evaluation
+        from .device_matching import DeviceEvaluation, pack_evaluation, pack_ground_truth
         if border_pixels not in ("half", "include", "exclude"):
             raise ValueError("Unexpected value for `border_pixels`: '{}'".format(border_pixels))
+        if self._collector is not None:
+            # the detections never left the device: rank and segment them there (dj_eval_rank), upload the ground truth
+            ranked, offsets = self._collector.rank()
+            sizes = np.diff(offsets)[1:]
+            dev = DeviceEvaluation.from_device(pack_ground_truth(self, ignore_neutral_boxes), ranked, offsets)
+        else:
+            sizes = [len(self.prediction_results[class_id]) for class_id in range(1, self.n_classes + 1)]
+            dev = DeviceEvaluation(pack_evaluation(self, ignore_neutral_boxes))
+            dev.upload()
         if verbose:
             for class_id in range(1, self.n_classes + 1):
-                if len(self.prediction_results[class_id]) == 0:
+                if sizes[class_id - 1] == 0:
                     print("No predictions for class {}/{}".format(class_id, self.n_classes))
-        dev = DeviceEvaluation(pack_evaluation(self, ignore_neutral_boxes))
-        dev.upload()
         tp, fp = dev.match(matching_iou_threshold, border_pixels)
         cum_tp, cum_fp = dev.precision_recall_ap(None, 1)[:2]
         self.true_positives, self.false_positives = dev.per_class(tp, int), dev.per_class(fp, int)
@@ -354,6 +406,21 @@ class Evaluator(object):
         self.mean_average_precision = np.average(self.average_precisions[1:])
         if ret:
             return self.mean_average_precision
+
+
+def append_batch_results(results, y_pred, batch_image_ids, seen, n_images, round_confidences, pred_format):
+    """One batch of decoded, inverse-transformed detections (a list of [n][6] arrays) -> tuples appended to
+    `results[class_id]`, image after image; `seen` images came before this batch and the dataset has `n_images`."""
+    p = pred_format
+    for k, batch_item in enumerate(y_pred):
+        if seen + k >= n_images:            # the last batch wraps around the dataset
+            break
+        image_id = batch_image_ids[k]
+        for box in np.asarray(batch_item).reshape(-1, 6):
+            conf = round(float(box[p["conf"]]), round_confidences) if round_confidences else box[p["conf"]]
+            results[int(box[p["class_id"]])].append(
+                (image_id, conf, round(float(box[p["xmin"]]), 1), round(float(box[p["ymin"]]), 1),
+                 round(float(box[p["xmax"]]), 1), round(float(box[p["ymax"]]), 1)))
 
 
 def apply_inverse_transforms(y_pred_decoded, inverse_transforms):

@@ -530,11 +530,16 @@ class Model(object):
                 tot += l2 * float((self._store["flat"][a:b] ** 2).sum())
         return tot
 
-    def predict_on_batch(self, x):
+    def predict_on_batch(self, x, to_host=True):
+        """`to_host=False`: the outputs as the CUDA tensors the plan owns, without a download.  The next forward pass of
+        this batch size overwrites them: consume them on the launch stream before it."""
         b = self._as_list(x)[0].shape[0]
         plan = self._plan(b, False, False)
         self._upload(plan, x, None)
         plan.run_forward()
+        if not to_host:
+            outs = [v.buf.detach() for v in plan.outputs]
+            return outs[0] if len(outs) == 1 else outs
         outs = [v.buf.detach().cpu().numpy() for v in plan.outputs]
         return outs[0] if len(outs) == 1 else outs
 

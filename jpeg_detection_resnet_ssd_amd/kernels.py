@@ -569,3 +569,60 @@ def eval_precision_recall_ap(tp, fp, class_offsets, num_gt, thresholds, cum_tp, 
                                            ptr(thresholds), thresholds.numel(), ptr(cum_tp), ptr(cum_fp), ptr(precision),
                                            ptr(recall), ptr(ap), _stream()), "dj_eval_precision_recall_ap")
     return ap
+
+
+def eval_collect(decoded, n_valid, desc_host, first_ordinal, n_classes, n_images, conf_digits, boxes_final, records, counters):
+    """dj_eval_collect: append the rows of `decoded` ([B][rows][6] float32 CUDA tensor) whose class id is not 0, for the
+    first `n_valid` images, to `records` (the dict of eval_utils/device_matching.py:DeviceCollector: rec_class, rec_image,
+    rec_ordinal int32, rec_conf float32, rec_conf64 float64, rec_boxes float32 [capacity][4]) behind counters[0].
+    `desc_host`: one device_matching.DESC_DTYPE record per image, on the host.  One launch, no synchronisation."""
+    import ctypes
+    import numpy as np
+    from .eval_utils.device_matching import DESC_DTYPE
+    assert decoded.dim() == 3 and decoded.shape[2] == 6, "decoded: expected [B][rows][6]"
+    b, rows = int(decoded.shape[0]), int(decoded.shape[1])
+    capacity = records["rec_class"].numel()
+    _check_eval_tensor(decoded, "decoded", torch.float32, b * rows * 6)
+    for name, dtype, numel in (("rec_class", torch.int32, capacity), ("rec_image", torch.int32, capacity),
+                               ("rec_ordinal", torch.int32, capacity), ("rec_conf", torch.float32, capacity),
+                               ("rec_conf64", torch.float64, capacity), ("rec_boxes", torch.float32, capacity * 4)):
+        _check_eval_tensor(records[name], name, dtype, numel)
+    _check_eval_tensor(counters, "counters", torch.int32, 4)
+    assert DESC_DTYPE.itemsize == 16 and ctypes.sizeof(ctypes.c_int) == 4, "descriptor layouts disagree"
+    assert isinstance(desc_host, np.ndarray) and desc_host.dtype == DESC_DTYPE and desc_host.shape == (b,) \
+        and desc_host.flags.c_contiguous, "desc_host: expected a contiguous array of one DESC_DTYPE record per image"
+    check(_L().dj_eval_collect(ptr(decoded), b, rows, int(n_valid), desc_host.ctypes.data, int(first_ordinal), int(n_classes),
+                               int(n_images), int(conf_digits), int(bool(boxes_final)), ptr(records["rec_class"]),
+                               ptr(records["rec_image"]), ptr(records["rec_ordinal"]), ptr(records["rec_conf"]),
+                               ptr(records["rec_conf64"]), ptr(records["rec_boxes"]), capacity, ptr(counters), _stream()),
+          "dj_eval_collect")
+    return counters
+
+
+def eval_rank_workspace_bytes(capacity, n_classes):
+    return check(_L().dj_eval_rank_workspace_bytes(int(capacity), int(n_classes)), "dj_eval_rank_workspace_bytes")
+
+
+def eval_rank(records, n_classes, n_images, counters, out, workspace):
+    """dj_eval_rank: the counters[0] records of `records` -> `out`, a dict of CUDA tensors sized by the capacity:
+    class_offsets [n_classes + 2], pred_class, pred_image, seg_class, seg_image, seg_ranks [capacity], seg_offsets
+    [capacity + 1] int32, pred_conf [capacity], pred_boxes [capacity][4] float32; counters[2] receives the number of
+    segments.  `workspace`: a uint8 CUDA tensor of `eval_rank_workspace_bytes` bytes.  No synchronisation."""
+    capacity = records["rec_class"].numel()
+    for name, dtype, numel in (("rec_class", torch.int32, capacity), ("rec_image", torch.int32, capacity),
+                               ("rec_conf", torch.float32, capacity), ("rec_boxes", torch.float32, capacity * 4)):
+        _check_eval_tensor(records[name], name, dtype, numel)
+    for name, dtype, numel in (("class_offsets", torch.int32, n_classes + 2), ("pred_class", torch.int32, capacity),
+                               ("pred_image", torch.int32, capacity), ("pred_conf", torch.float32, capacity),
+                               ("pred_boxes", torch.float32, capacity * 4), ("seg_class", torch.int32, capacity),
+                               ("seg_image", torch.int32, capacity), ("seg_offsets", torch.int32, capacity + 1),
+                               ("seg_ranks", torch.int32, capacity)):
+        _check_eval_tensor(out[name], name, dtype, numel)
+    _check_eval_tensor(counters, "counters", torch.int32, 4)
+    _check_eval_tensor(workspace, "workspace", torch.uint8, workspace.numel())
+    check(_L().dj_eval_rank(ptr(records["rec_class"]), ptr(records["rec_image"]), ptr(records["rec_conf"]),
+                            ptr(records["rec_boxes"]), capacity, int(n_classes), int(n_images), ptr(counters),
+                            ptr(out["class_offsets"]), ptr(out["pred_class"]), ptr(out["pred_image"]), ptr(out["pred_conf"]),
+                            ptr(out["pred_boxes"]), ptr(out["seg_class"]), ptr(out["seg_image"]), ptr(out["seg_offsets"]),
+                            ptr(out["seg_ranks"]), ptr(workspace), workspace.numel(), _stream()), "dj_eval_rank")
+    return out

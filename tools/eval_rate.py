@@ -7,8 +7,14 @@ device path:
   (b) device: Evaluator(device_matching=True), the same three calls, and split into
               packing (python lists -> flat arrays, rank order, segments; host), upload, dj_eval_match and
               dj_eval_precision_recall_ap (by device events), download of every result array
+  (c) collection, from the decoded [B][detections][6] batches as the DecodeDetections layer leaves them on the GPU to the
+      arrays dj_eval_match reads, on the same detections with a `Resize` inverter per image:
+      host:   per batch download, padding mask, apply_inverse_transforms, the per-box loop; then pack_evaluation and upload
+              (`--host-reps` runs)
+      device: Evaluator(device_predictions=True)'s path: dj_eval_collect per batch, then dj_eval_rank with its one small
+              download
 
-    python tools/eval_rate.py [--images 4952] [--detections 200] [--reps 5] [--host-reps 1]
+    python tools/eval_rate.py [--images 4952] [--detections 200] [--reps 5] [--host-reps 1] [--batch-size 8]
 
 Medians over the repetitions after warm-up; every timed window ends in a device synchronise.  The results of the two
 paths are compared for equality.  Prints one JSON line at the end."""
@@ -23,8 +29,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from jpeg_detection_resnet_ssd_amd.eval_utils.average_precision_evaluator import Evaluator
-from jpeg_detection_resnet_ssd_amd.eval_utils.device_matching import DeviceEvaluation, pack_evaluation
+from jpeg_detection_resnet_ssd_amd.eval_utils.average_precision_evaluator import (Evaluator, append_batch_results,
+                                                                                 apply_inverse_transforms)
+from jpeg_detection_resnet_ssd_amd.eval_utils.device_matching import (RANKED_FIELDS, DeviceCollector, DeviceEvaluation,
+                                                                      pack_evaluation)
 
 
 def median_ms(fn, reps, warmup=1):
@@ -68,6 +76,7 @@ def make_dataset(rng, n_images, n_classes, detections):
     copies of the objects (some repeated) filled up to `detections` with boxes anywhere, classes drawn at random, the
     confidence of a good detection high and the others' skewed towards the 0.01 cut-off, as an SSD's top-200 are."""
     labels, neutral = [], []
+    decoded = np.zeros((n_images, detections, 6), dtype=np.float32)    # the same detections as a decoded tensor
     results = [list() for _ in range(n_classes + 1)]
     for i in range(n_images):
         n = 1 + int(rng.poisson(1.5))
@@ -86,10 +95,66 @@ def make_dataset(rng, n_images, n_classes, detections):
         boxes = np.where(good[:, None], boxes, np.stack([rx, ry, rx + rw, ry + rh], axis=1))
         pcls = np.where(good, cls[src], rng.integers(1, n_classes + 1, m))
         conf = np.where(good, rng.uniform(0.3, 1.0, m), 0.01 + 0.5 * rng.random(m) ** 4).astype(np.float32)
+        decoded[i, :, 0], decoded[i, :, 1], decoded[i, :, 2:] = pcls, conf, boxes
         for k in range(m):
             results[int(pcls[k])].append((image_id, conf[k], round(float(boxes[k, 0]), 1), round(float(boxes[k, 1]), 1),
                                           round(float(boxes[k, 2]), 1), round(float(boxes[k, 3]), 1)))
-    return Dataset(labels, neutral), results
+    return Dataset(labels, neutral), results, decoded
+
+
+def collection_stage(args, data, decoded, res):
+    """(c): both paths start from the decoded batches resident on the GPU and end with the matching's inputs there."""
+    from jpeg_detection_resnet_ssd_amd.data.ssd_augment import Resize
+    inverter = Resize(300, 300)(np.zeros((375, 500, 3), dtype=np.uint8), return_inverter=True)[1]
+    pred_format = {"class_id": 0, "conf": 1, "xmin": 2, "ymin": 3, "xmax": 4, "ymax": 5}
+    n, ids = len(decoded), data.image_ids
+    batches = [torch.from_numpy(decoded[i:i + args.batch_size]).cuda() for i in range(0, n, args.batch_size)]
+    out = {}
+
+    def host_path():
+        results, seen = [list() for _ in range(args.classes + 1)], 0
+        for t in batches:
+            y = t.cpu().numpy()
+            y_pred = [y[i][y[i, :, 0] != 0] for i in range(len(y))]
+            y_pred = apply_inverse_transforms(y_pred, [[inverter]] * len(y))
+            append_batch_results(results, y_pred, ids[seen:seen + len(y)], seen, n, False, pred_format)
+            seen += len(y)
+        out["lists_s"] = time.perf_counter()
+        ev = Evaluator(model=None, n_classes=args.classes, data_generator=data)
+        ev.prediction_results = results
+        out["packed"] = pack_evaluation(ev, True)
+        DeviceEvaluation(out["packed"]).upload()
+
+    def collect():
+        c, seen = DeviceCollector(args.classes, ids, 0), 0
+        for t in batches:
+            c.add(t, len(t), ids[seen:seen + len(t)], [[inverter]] * len(t))
+            seen += len(t)
+        out["collector"] = c
+
+    def rank():
+        out["collector"].ranked = None
+        out["collector"].rank()
+
+    def device_path():
+        collect()
+        rank()
+
+    res["batches"] = len(batches)
+    res["device_collect_rank_ms"] = median_ms(device_path, args.reps)
+    res["device_collect_ms"] = median_ms(collect, args.reps)
+    res["device_rank_ms"] = median_ms(rank, args.reps)
+    t0 = time.perf_counter()
+    res["host_collect_pack_upload_ms"] = median_ms(host_path, args.host_reps, warmup=0)
+    res["host_lists_ms"] = (out["lists_s"] - t0) * 1e3 if args.host_reps == 1 else None
+    res["host_over_device_collection"] = res["host_collect_pack_upload_ms"][0] / res["device_collect_rank_ms"][0]
+    ranked = out["collector"].rank()[0]
+    same = True
+    for name in RANKED_FIELDS:
+        a, b = ranked[name].cpu().numpy(), getattr(out["packed"], name)
+        bits = lambda v: np.ascontiguousarray(v).view(np.uint32) if v.dtype == np.float32 else v
+        same = same and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(bits(a), bits(b))
+    res["device_collection_equals_host"] = bool(same)
 
 
 def main():
@@ -99,10 +164,11 @@ def main():
     ap.add_argument("--detections", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-reps", type=int, default=1)
+    ap.add_argument("--batch-size", type=int, default=8)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "eval_rate.py measures on the GPU"
     rng = np.random.default_rng(0)
-    data, results = make_dataset(rng, args.images, args.classes, args.detections)
+    data, results, decoded = make_dataset(rng, args.images, args.classes, args.detections)
     settings = dict(ignore_neutral_boxes=True, matching_iou_threshold=0.5, border_pixels="include",
                     sorting_algorithm="mergesort", verbose=False)
 
@@ -157,6 +223,7 @@ def main():
             same = same and np.array_equal(getattr(host_ev, name)[c], getattr(dev_ev, name)[c], equal_nan=True)
     res["device_equals_host"] = bool(same)
     res["mAP"] = float(np.average(dev_ev.average_precisions[1:]))
+    collection_stage(args, data, decoded, res)
     print(json.dumps(res), flush=True)
 
 

@@ -553,6 +553,38 @@ int dj_ssd_photometric(unsigned char* src, long src_bytes, const dj_patch_resize
                        const dj_patch_resize_desc* desc_host, const dj_ssd_photo_params* params_dev,
                        const dj_ssd_photo_params* params_host, int batch, void* stream);
 
+/* ---- RGB pixels of baseline / extended-sequential JPEG files from their entropy-decoded RAW (not de-quantised) int16
+ * coefficient planes (include/dj_jpeg_decode.h: dj_jpeg_read_raw_batch), byte for byte what data/jpeg_pixels.py:jpeg_pixels_host
+ * states in numpy and Pillow's Image.open(f).convert("RGB") returns: coefficient * table in int32, libjpeg's integer "slow"
+ * inverse DCT (13-bit constants; column pass descaled by 11 bits, row pass by 18, + 128, clamp), the triangle upsampling
+ * filters for a chroma component wider than 2 samples (neighbours past the component's real down-sampled extent are the
+ * edge sample) and plain replication for a narrower one, the 16-bit fixed-point YCbCr -> RGB; one component is gray,
+ * replicated.  Per image only the rectangle rows [ya, yb) x columns [xa, xb) is reconstructed, into dst + dst_offset with
+ * rows dst_stride apart: where a staging plan would have copied decoded pixels.  Component c's plane is blocks_h[c] x
+ * blocks_w[c] x 64 values in natural order at coef + coef_offset[c] (bytes, even) and its table 64 ints at tables +
+ * table_offset + 64 c.  The inverse DCT runs over block rows [by0, by1) x columns [bx0, bx1) of each component -- at least
+ * the blocks the rectangle's samples and their filter neighbours lie in -- and leaves them as a uint8 plane of
+ * 8 (bx1 - bx0) bytes per row at scratch + sample_offset[c] (a multiple of 8); these regions come in (image, component)
+ * order and do not overlap.  coef / desc_dev / tables / dst / scratch are DEVICE pointers, desc_host the HOST copy of the
+ * descriptors, read during the call only: every offset, grid, range and rectangle is checked against the sizes given
+ * before anything is launched, and an error writes nothing.  Two launches, no synchronisation: capturable. ---- */
+typedef struct dj_jpeg_pixels_desc {
+  long coef_offset[3];
+  long sample_offset[3];
+  long dst_offset;
+  long dst_stride;       /* >= 3 * (xb - xa) */
+  int table_offset;      /* ints */
+  int n_components;      /* 1 (gray) or 3 (YCbCr) */
+  int h_samp, v_samp;    /* luma over chroma: 1x1, 2x1 or 2x2 (1x1 for gray) */
+  int height, width;     /* of the image */
+  int ya, yb, xa, xb;
+  int blocks_h[3], blocks_w[3];
+  int by0[3], by1[3], bx0[3], bx1[3];
+} dj_jpeg_pixels_desc;
+int dj_jpeg_pixels(const unsigned char* coef, long coef_bytes, const dj_jpeg_pixels_desc* desc_dev,
+                   const dj_jpeg_pixels_desc* desc_host, int n, const int* tables, long table_ints, unsigned char* dst,
+                   long dst_bytes, unsigned char* scratch, long scratch_bytes, void* stream);
+
 /* ---- Pascal-VOC evaluation (L/eval_utils/average_precision_evaluator.py:570-925): `Evaluator.match_predictions`,
  * `compute_precision_recall` and `compute_average_precisions(mode='sample')` with results equal bit for bit to the host
  * methods (float64, their operation order; eval_utils/device_matching.py packs the inputs and restates the segment-wise

@@ -63,8 +63,8 @@ def build_library(force=False, verbose=False):
 def build_jpeg_library(force=False):
     """Host-only JPEG coefficient reader (csrc/dj_jpeg.cpp -> csrc/libdj_jpeg.so), plain g++."""
     src = os.path.join(CSRC, "dj_jpeg.cpp")
-    hdr = os.path.join(CSRC, "..", "..", "include", "dj_jpeg.h")
-    if force or _newer([src, hdr], JPEG_LIB_PATH):
+    hdrs = [os.path.join(CSRC, "..", "..", "include", h) for h in ("dj_jpeg.h", "dj_jpeg_decode.h")]
+    if force or _newer([src] + hdrs, JPEG_LIB_PATH):
         cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", src, "-o",
                JPEG_LIB_PATH]
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -41,6 +41,13 @@ class PatchResizeDesc(Structure):   # dj_patch_resize_desc
                                         "h_taps", "h_ksize", "v_bounds", "v_taps", "v_ksize")])
 
 
+class JpegPixelsDesc(Structure):   # dj_jpeg_pixels_desc
+    _fields_ = ([("coef_offset", c_long * 3), ("sample_offset", c_long * 3), ("dst_offset", c_long), ("dst_stride", c_long)]
+                + [(n, c_int) for n in ("table_offset", "n_components", "h_samp", "v_samp", "height", "width", "ya", "yb",
+                                        "xa", "xb")]
+                + [(n, c_int * 3) for n in ("blocks_h", "blocks_w", "by0", "by1", "bx0", "bx1")])
+
+
 class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
@@ -179,6 +186,8 @@ SIGNATURES = {
     "dj_patch_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
                                 c_long, c_void_p, c_long, c_void_p]),
     "dj_ssd_photometric": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dj_jpeg_pixels": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                               c_long, c_void_p]),
     "dj_eval_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
                               c_void_p]),

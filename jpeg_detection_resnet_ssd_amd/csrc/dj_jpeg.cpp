@@ -1,13 +1,15 @@
 // JPEG -> quantised / de-quantised DCT coefficients, entropy decoding only (ITU-T T.81 sequential Huffman mode).
 // Host code behind include/dj_jpeg.h; takes the place of jpeg2dct (libjpeg's jpeg_read_coefficients) in the
 // reference's data generators (object_detection_2d_data_generator_dct_j2d.py:1167-1195).
-#include "../../include/dj_jpeg.h"
+#include "../../include/dj_jpeg_decode.h"
 
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -84,10 +86,12 @@ struct BitReader {
   int nbits = 0;
   int marker = 0;  // pending marker byte seen in the entropy-coded segment (0 = none)
   const unsigned char* marker_pos = nullptr;  // its 0xFF
+  bool ran_out = false;  // bits were asked for past the end of the data with no marker seen: zeros were fed
 
   void fill() {
     while (nbits <= 56) {
       unsigned b = 0;
+      if (!marker && p >= end) ran_out = true;
       if (!marker && p < end) {
         b = *p;
         if (b == 0xFF) {
@@ -99,6 +103,7 @@ struct BitReader {
             while (q < end && *q == 0xFF) ++q;     // fill bytes
             marker_pos = q - 1;
             marker = (q < end) ? *q : 0xD9;
+            if (q >= end) ran_out = true;          // the data ends inside a marker: the 0xD9 is made up
             p = (q < end) ? q + 1 : end;
             b = 0;
           }
@@ -158,11 +163,16 @@ struct Decoder {
   int width = 0, height = 0, ncomp = 0, sof = -1;
   int hmax = 1, vmax = 1;
   int restart_interval = 0;
+  int precision = 0;
+  bool saw_jfif = false, saw_adobe = false;
+  int adobe_transform = 0;
   uint16_t qt[4][64];
   bool qt_present[4] = {false, false, false, false};
   Huff dc[4], ac[4];
   Component comp[4];
   bool saw_sof = false;
+  bool strict = false;   // a scan that ends before its last MCU, or a file without EOI, is an error (no zero-filled tail)
+  bool saw_eoi = false;
   Scratch* scratch = nullptr;
 
   static int be16(const unsigned char* p) { return (p[0] << 8) | p[1]; }
@@ -202,6 +212,7 @@ struct Decoder {
     // the new geometry into the old planes
     if (saw_sof) return fail("second frame header (SOF) in one file");
     if (len < 6) return fail("truncated SOF");
+    precision = p[0];
     if (p[0] != 8) return fail("only 8-bit JPEG is supported (precision %d)", p[0]);
     height = be16(p + 1);
     width = be16(p + 3);
@@ -328,6 +339,7 @@ struct Decoder {
           }
         }
       }
+    if (strict && br.ran_out) return fail("truncated scan: the entropy-coded data ends before the last MCU");
     // position after the scan: the pending marker (if the reader met one) or search for the next
     if (br.marker) {
       *next = br.marker_pos;
@@ -356,7 +368,10 @@ struct Decoder {
         continue;
       }
       p += 2;
-      if (m == 0xD9) break;                                  // EOI
+      if (m == 0xD9) {                                       // EOI
+        saw_eoi = true;
+        break;
+      }
       if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // standalone
       if (p + 2 > end) return fail("truncated marker segment");
       int len = be16(p);
@@ -377,6 +392,13 @@ struct Decoder {
           return 0;
         }
         return fail("unsupported JPEG process SOF%d (only baseline / extended sequential Huffman)", m - 0xC0);
+      } else if (m == 0xE0) {                                 // libjpeg's examine_app0: "JFIF\0" and 14 bytes
+        if (blen >= 14 && !memcmp(body, "JFIF\0", 5)) saw_jfif = true;
+      } else if (m == 0xEE) {                                 // examine_app14: "Adobe", transform in the 12th byte
+        if (blen >= 12 && !memcmp(body, "Adobe", 5)) {
+          saw_adobe = true;
+          adobe_transform = body[11];
+        }
       } else if (m == 0xDD) {
         if (blen < 2) return fail("bad DRI");
         restart_interval = be16(body);
@@ -392,6 +414,7 @@ struct Decoder {
     }
     if (!saw_sof) return fail("no frame header");
     if (!headers_only && !any_scan) return fail("no scan data");
+    if (!headers_only && strict && !saw_eoi) return fail("truncated file: no end-of-image marker");
     return 0;
   }
 
@@ -429,6 +452,77 @@ struct Decoder {
 };
 
 thread_local Scratch g_scratch;
+
+// What the pixel reconstruction on the GPU (csrc/dj_jpegpix.hip) restates: sequential Huffman, 8-bit, gray or libjpeg's
+// YCbCr (jdapimin.c:default_decompress_parms), luma 1x1 / 2x1 / 2x2 over 1x1 chroma, every table present.
+bool device_decodable(const Decoder& d) {
+  if ((d.sof != 0 && d.sof != 1) || d.precision != 8) return false;
+  for (int c = 0; c < d.ncomp; ++c)
+    if (!d.qt_present[d.comp[c].tq]) return false;
+  if (d.ncomp == 1) return true;
+  if (d.ncomp != 3) return false;
+  const bool rgb_ids = d.comp[0].id == 'R' && d.comp[1].id == 'G' && d.comp[2].id == 'B';
+  const bool ycc = d.saw_jfif || (d.saw_adobe ? d.adobe_transform == 1 : !rgb_ids);
+  if (!ycc) return false;
+  const int h = d.comp[0].h, v = d.comp[0].v;
+  if (!((h == 1 && v == 1) || (h == 2 && v == 1) || (h == 2 && v == 2))) return false;
+  return d.comp[1].h == 1 && d.comp[1].v == 1 && d.comp[2].h == 1 && d.comp[2].v == 1;
+}
+
+// Scratch planes of the batch reader's workers, kept from call to call (a worker thread lives for one call only, so
+// thread_local planes would be allocated afresh every batch)
+std::mutex g_pool_mutex;
+std::vector<std::unique_ptr<Scratch>> g_pool;
+
+std::unique_ptr<Scratch> borrow_scratch() {
+  std::lock_guard<std::mutex> lock(g_pool_mutex);
+  if (g_pool.empty()) return std::unique_ptr<Scratch>(new Scratch);
+  std::unique_ptr<Scratch> s = std::move(g_pool.back());
+  g_pool.pop_back();
+  return s;
+}
+
+void return_scratch(std::unique_ptr<Scratch> s) {
+  std::lock_guard<std::mutex> lock(g_pool_mutex);
+  if (g_pool.size() < 64) g_pool.push_back(std::move(s));
+}
+
+int check_raw_planes(const Decoder& d, long buffer_bytes, const long* offsets, const long* capacity) {
+  for (int c = 0; c < d.ncomp; ++c) {
+    const long need = (long)d.comp[c].blocks_h * d.comp[c].blocks_w * 64;
+    if (capacity[c] < need) return fail("plane %d too small (%ld < %ld)", c, capacity[c], need);
+    if (offsets[c] < 0 || offsets[c] % 2 != 0 || offsets[c] > buffer_bytes || need > (buffer_bytes - offsets[c]) / 2)
+      return fail("plane %d: %ld values at byte offset %ld leave the buffer of %ld bytes (or the offset is odd)", c, need,
+                  offsets[c], buffer_bytes);
+  }
+  return 0;
+}
+
+int read_raw_into(const unsigned char* data, long size, unsigned char* buffer, long buffer_bytes, const long* offsets,
+                  const long* capacity, Scratch* scratch) {
+  if (!data || size <= 0) return fail("null or empty file");
+  {
+    // the frame header against the caller's planes BEFORE any scan is decoded: a file whose header asks for more than
+    // the caller laid out is refused without its (possibly huge) planes ever being allocated here
+    Decoder h;
+    h.data = data;
+    h.size = size;
+    h.scratch = scratch;
+    if (h.run(true)) return -1;
+    if (h.sof != 0 && h.sof != 1) return fail("unsupported JPEG process SOF%d", h.sof);
+    if (check_raw_planes(h, buffer_bytes, offsets, capacity)) return -1;
+  }
+  Decoder d;
+  d.data = data;
+  d.size = size;
+  d.scratch = scratch;
+  d.strict = true;       // Pillow refuses a truncated file; so does the path that stands in for it
+  if (d.run(false)) return -1;
+  if (check_raw_planes(d, buffer_bytes, offsets, capacity)) return -1;
+  for (int c = 0; c < d.ncomp; ++c)
+    if (d.emit<short>(c, 0, reinterpret_cast<short*>(buffer + offsets[c]))) return -1;
+  return 0;
+}
 
 int decode_one_f32(const unsigned char* data, long size, int normalized, float* y, float* cb, float* cr, int yh, int yw,
                    int ch, int cw, Scratch* scratch) {
@@ -508,4 +602,64 @@ extern "C" int dj_jpeg_decode_batch_f32(const unsigned char* const* data, const 
     return fail("image %d failed", failed.load());
   }
   return 0;
+}
+
+extern "C" int dj_jpeg_read_decode_info(const unsigned char* data, long size, dj_jpeg_decode_info* info) {
+  if (!data || !info || size <= 0) return fail("read_decode_info: null argument");
+  Decoder d;
+  d.data = data;
+  d.size = size;
+  d.scratch = &g_scratch;
+  if (d.run(true)) return -1;
+  if (!d.saw_sof) return fail("no frame header");
+  memset(info, 0, sizeof(*info));
+  d.fill_info(&info->base);
+  for (int c = 0; c < d.ncomp; ++c) info->component_id[c] = d.comp[c].id;
+  info->saw_jfif = d.saw_jfif;
+  info->saw_adobe = d.saw_adobe;
+  info->adobe_transform = d.adobe_transform;
+  info->precision = d.precision;
+  info->device_decodable = device_decodable(d);
+  return 0;
+}
+
+extern "C" int dj_jpeg_read_raw_batch(const unsigned char* const* data, const long* sizes, int n, unsigned char* buffer,
+                                      long buffer_bytes, const long* plane_offsets, const long* plane_capacity,
+                                      int* status, int n_threads) {
+  if (!data || !sizes || !buffer || !plane_offsets || !plane_capacity || !status || n <= 0 || buffer_bytes <= 0)
+    return fail("read_raw_batch: null argument");
+  if (n_threads < 1) n_threads = 1;
+  if (n_threads > n) n_threads = n;
+  std::atomic<int> next(0), failures(0), first(n);
+  std::vector<std::string> msgs((size_t)n_threads);
+  std::vector<int> msg_of((size_t)n_threads, n);
+  auto work = [&](int t) {
+    std::unique_ptr<Scratch> scratch = borrow_scratch();
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= n) break;
+      status[i] = read_raw_into(data[i], sizes[i], buffer, buffer_bytes, plane_offsets + 4 * i, plane_capacity + 4 * i,
+                                scratch.get());
+      if (status[i]) {
+        failures.fetch_add(1);
+        if (i < msg_of[(size_t)t]) {      // this worker's lowest failing file
+          msg_of[(size_t)t] = i;
+          msgs[(size_t)t] = g_err;
+        }
+        int seen = first.load();
+        while (i < seen && !first.compare_exchange_weak(seen, i)) {
+        }
+      }
+    }
+    return_scratch(std::move(scratch));
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < n_threads; ++t) pool.emplace_back(work, t);
+  work(0);
+  for (auto& th : pool) th.join();
+  if (failures.load()) {
+    for (int t = 0; t < n_threads; ++t)
+      if (msg_of[(size_t)t] == first.load()) fail("image %d: %s", first.load(), msgs[(size_t)t].c_str());
+  }
+  return failures.load();
 }

@@ -5,7 +5,9 @@ resize) share, none of which knows what a descriptor means:
     of allowed filters;
   * `TapsPool`: the deduplicated int32 pool of bounds and taps of one batch;
   * `StagedPlan`: descriptors, pool and the layout of one staging blob whose parts each start at a multiple of 64 bytes,
-    with `fill`, `views` and (in the subclass) `launch`;
+    with `fill`, `views` and (in the subclass) `launch`; and, for the items of a batch that are `CoefficientImage`s
+    (data/jpeg_pixels.py: a JPEG file's bytes in place of its decoded pixels), the decode descriptors, tables and raw
+    coefficient planes that dj_jpeg_pixels turns into those items' staged pixels on the GPU;
   * `ResidentBuffers`: the per-device buffers an emitter keeps and the staging, upload and launch of one plan (`run`);
   * `run_once`: the same with fresh buffers, for callers outside `Model`.
 
@@ -23,6 +25,8 @@ import functools
 import math
 
 import numpy as np
+
+from .jpeg_pixels import CoefficientImage
 
 PRECISION_BITS = 32 - 8 - 2      # Pillow's fixed-point fraction for 8-bit images
 
@@ -165,6 +169,8 @@ def resample_pass(img, bounds, taps):
 
 
 def check_image(image):
+    if isinstance(image, CoefficientImage):      # stands for the (H, W, 3) uint8 image its file decodes to
+        return image
     image = np.asarray(image)
     if image.ndim != 3 or image.shape[2] != 3 or image.dtype != np.uint8 or image.shape[0] < 1 or image.shape[1] < 1:
         raise ValueError("expected an (H, W, 3) uint8 image, got %s %s" % (image.dtype, image.shape))
@@ -196,6 +202,7 @@ def resize_host(image, size, resample=None, allowed=RESTATED):
 
 # ---- one staging blob per batch ---------------------------------------------------------------------------------------------
 ALIGN = 64
+MAX_FILL_THREADS = 16      # of `fill`'s batch reader when the caller names no count: past that a batch of 32 files gains nothing
 
 
 def round_up(n, a=ALIGN):
@@ -222,14 +229,91 @@ class TapsPool(object):
         return np.concatenate(self.chunks).astype(np.int32, copy=False)
 
 
+# dj_jpeg_pixels_desc (include/dj_hip.h), C layout
+DECODE_DTYPE = np.dtype([("coef_offset", np.int64, 3), ("sample_offset", np.int64, 3), ("dst_offset", np.int64),
+                         ("dst_stride", np.int64)]
+                        + [(n, np.int32) for n in ("table_offset", "n_components", "h_samp", "v_samp", "height", "width",
+                                                   "ya", "yb", "xa", "xb")]
+                        + [(n, np.int32, 3) for n in ("blocks_h", "blocks_w", "by0", "by1", "bx0", "bx1")], align=True)
+
+
+def needed_samples(a, b, factor, extent):
+    """[lo, hi] of the samples of a component sampled `factor` (1 or 2) times coarser than the image, of real extent
+    `extent`, that image rows / columns a..b-1 read -- the triangle filter's neighbour included."""
+    s = factor - 1
+    return max((a >> s) - s, 0), min(((b - 1) >> s) + s, extent - 1)
+
+
 class StagedPlan(object):
     """Everything the kernels of one ragged batch need except the pixels' bytes: `desc` (one DESC_DTYPE record per
     image), `pool`, `src_bytes` / `scratch_bytes`, `out_shape` and the layout of one staging blob.  A subclass fills
     `desc` in its geometry loop, then calls `_lay_out` with its parts in order: (name, array), (name, None) for a part
     this batch does not carry, and ("src", src_bytes) for the pixels, which its `_fill_pixels` writes.  Part `name`
     starts at `<name>_offset`, a multiple of 64; the blob ends with its last part (`nbytes`).  `launch` issues the
-    plan's kernels in order."""
+    plan's kernels in order.
+
+    A batch in which some items are `CoefficientImage`s: the subclass calls `_plan_decode` with, per item, the rectangle
+    it stages and where that rectangle's pixels lie in the "src" part, and puts the parts it returns BEHIND its own.  Such
+    items' pixels are not copied by `_fill_pixels`: `fill` has the batch reader write their raw coefficient planes
+    into the blob, and `launch_decode` (first in the subclass's `launch`) runs dj_jpeg_pixels, which writes the
+    rectangles where `_fill_pixels` would have.  Whole planes are staged, about 3 bytes per image pixel, because the
+    reader's workers emit whole planes, each copied from the worker's own planes to its place in the blob.  The sample planes of the inverse DCT take scratch behind `scratch_bytes` as the
+    subclass left it.  A batch without such items has no such parts: its blob and its launches are what they were."""
     DESC_DTYPE = None
+    decode = None          # DECODE_DTYPE records of the CoefficientImage items that stage something; None without any
+
+    def _plan_decode(self, images, rects, dst):
+        """images: the batch, any item possibly a `CoefficientImage`; rects[i] = (ya, yb, xa, xb) staged of item i (empty:
+        nothing); dst[i] = (byte offset in the "src" part, row stride) of that rectangle.  Grows `scratch_bytes`; -> the
+        parts to lay out behind the plan's own ([] when no item needs decoding)."""
+        items = [i for i, (im, (ya, yb, xa, xb)) in enumerate(zip(images, rects))
+                 if isinstance(im, CoefficientImage) and yb > ya and xb > xa]
+        if not items:
+            return []
+        self.decode_items = items
+        self.decode = np.zeros(len(items), dtype=DECODE_DTYPE)
+        self.tables = np.zeros((len(items), 3, 64), dtype=np.int32)
+        self.plane_offsets = np.zeros((len(items), 4), dtype=np.int64)      # relative to the "coef" part
+        self.plane_capacity = np.zeros((len(items), 4), dtype=np.int64)
+        coef_off, scratch_off = 0, round_up(self.scratch_bytes)
+        for j, i in enumerate(items):
+            im, (ya, yb, xa, xb), d = images[i], rects[i], self.decode[j]
+            height, width = im.shape[:2]
+            h, v = im.sampling
+            d["dst_offset"], d["dst_stride"] = dst[i]
+            d["table_offset"], d["n_components"], d["h_samp"], d["v_samp"] = 192 * j, im.n_components, h, v
+            d["height"], d["width"], d["ya"], d["yb"], d["xa"], d["xb"] = height, width, ya, yb, xa, xb
+            self.tables[j] = im.tables()
+            for c, (bh, bw) in enumerate(im.grids()):
+                fy, fx = (1, 1) if c == 0 else (v, h)
+                r0, r1 = needed_samples(ya, yb, fy, -(-height // fy))
+                k0, k1 = needed_samples(xa, xb, fx, -(-width // fx))
+                d["blocks_h"][c], d["blocks_w"][c] = bh, bw
+                d["by0"][c], d["by1"][c], d["bx0"][c], d["bx1"][c] = r0 // 8, r1 // 8 + 1, k0 // 8, k1 // 8 + 1
+                d["coef_offset"][c], d["sample_offset"][c] = coef_off, scratch_off
+                self.plane_offsets[j, c], self.plane_capacity[j, c] = coef_off, bh * bw * 64
+                coef_off += round_up(bh * bw * 128)
+                scratch_off += round_up((r1 // 8 + 1 - r0 // 8) * (k1 // 8 + 1 - k0 // 8) * 64)
+        self.coef_bytes, self.scratch_bytes = coef_off, scratch_off
+        return [("decode", self.decode), ("tables", self.tables), ("coef", self.coef_bytes)]
+
+    def decode_views(self, blob):
+        """(descriptors, tables, coefficient planes) of a staging buffer or of its device copy, as `views` returns its
+        parts (numpy: a DECODE_DTYPE array, int32, bytes; torch: bytes all three)."""
+        desc = self.part(blob, self.decode_offset, self.decode, DECODE_DTYPE)
+        tables = self.part(blob, self.tables_offset, self.tables, np.int32)
+        return desc, tables, blob[self.coef_offset:self.coef_offset + self.coef_bytes]
+
+    def launch_decode(self, blob_host, blob_dev, scratch, stream=None):
+        """dj_jpeg_pixels for the plan's `CoefficientImage` items: their staged rectangles appear in the "src" part of
+        `blob_dev` as if the host had copied them there.  Nothing without such items."""
+        if self.decode is None:
+            return
+        from .. import kernels
+        desc_h, tables_h, _ = self.decode_views(blob_host)
+        desc_d, tables_d, coef_d = self.decode_views(blob_dev)
+        kernels.jpeg_pixels(coef_d, desc_d, desc_h, tables_d, tables_h,
+                            blob_dev[self.src_offset:self.src_offset + self.src_bytes], scratch, stream=stream)
 
     def _lay_out(self, parts):
         self.parts, end = [], 0
@@ -243,12 +327,22 @@ class StagedPlan(object):
                 end = offset + (content or 0)
         self.nbytes = end
 
-    def fill(self, staging, images):
+    def fill(self, staging, images, n_threads=None):
         """Write descriptors, pool, the pixels and whatever else the plan carries into `staging`, a uint8 numpy array of
-        at least `nbytes`."""
+        at least `nbytes`.  The raw coefficient planes of `CoefficientImage` items are entropy-decoded into it by
+        `n_threads` host threads (None: one per CPU this process may use, 16 at the most), each into planes of its own that
+        it then copies to their place in `staging`; a file that fails there raises ValueError."""
         for offset, content in self.parts:
             staging[offset:offset + content.size] = content
         self._fill_pixels(staging[self.src_offset:self.src_offset + self.src_bytes], images)
+        if self.decode is not None:
+            from ..jpeg2dct import numpy as reader
+            status = reader.read_raw_batch([images[i].data for i in self.decode_items], staging[:self.nbytes],
+                                           self.plane_offsets + self.coef_offset, self.plane_capacity,
+                                           n_threads if n_threads is not None else min(reader.default_threads(), MAX_FILL_THREADS))
+            if status.any():
+                raise ValueError("items %s of the batch could not be read: %s"
+                                 % ([self.decode_items[j] for j in np.flatnonzero(status)], reader.last_error()))
 
     def part(self, blob, offset, array, dtype=None):
         """The bytes of `array`'s part at `offset` of a staging buffer (a uint8 numpy array: viewed as `dtype`) or of its
@@ -276,13 +370,14 @@ def _uint8(n, device=None):
     return torch.empty(n, dtype=torch.uint8).pin_memory() if device is None else torch.empty(n, dtype=torch.uint8, device=device)
 
 
-def run_once(plan, images, device=None, out=None, stream=None):
-    """Pin, fill, upload and launch `plan` with fresh buffers -> its uint8 CUDA batch, complete on return."""
+def run_once(plan, images, device=None, out=None, stream=None, n_threads=None):
+    """Pin, fill (`n_threads` as for `StagedPlan.fill`), upload and launch `plan` with fresh buffers -> its uint8 CUDA
+    batch, complete on return."""
     import torch
     device = torch.device(device if device is not None else "cuda")
     staging = _uint8(plan.nbytes)
     host = staging.numpy()
-    plan.fill(host, images)
+    plan.fill(host, images, n_threads)
     blob = staging.to(device, non_blocking=True)
     if out is None:
         out = torch.empty(plan.out_shape, dtype=torch.uint8, device=device)
@@ -296,13 +391,15 @@ class ResidentBuffers(object):
     """An emitter's JPEG settings (`quality` / `tables` / `deconv` as for `DeviceDCTEmitter`) and its buffers, kept per
     device and grown on demand: two pinned staging buffers used in turn, each refilled only after the upload that last
     read it has finished (an event recorded behind the copy), the device copy of the staging buffer, the scratch of the
-    horizontal pass and the uint8 batch."""
+    horizontal pass and the uint8 batch.  `n_threads`: host threads `StagedPlan.fill` reads coefficient planes with
+    (None: its default)."""
 
-    def __init__(self, quality=75, tables=None, deconv=False):
+    def __init__(self, quality=75, tables=None, deconv=False, n_threads=None):
         from .jpeg_dct import resolve_tables
         self.tables = resolve_tables(quality, tables)
         self.quality = None if tables is not None else int(quality)
         self.deconv = bool(deconv)
+        self.n_threads = None if n_threads is None else int(n_threads)
         self._state = {}
 
     @staticmethod
@@ -327,7 +424,7 @@ class ResidentBuffers(object):
         for name, n in (("blob", plan.nbytes), ("scratch", plan.scratch_bytes), ("out", n_out)):
             st[name] = self._grown(st[name], n, device)
         host = slot[0].numpy()
-        plan.fill(host, images)
+        plan.fill(host, images, self.n_threads)
         st["blob"][:plan.nbytes].copy_(slot[0][:plan.nbytes], non_blocking=True)
         if slot[1] is None:
             slot[1] = torch.cuda.Event()

@@ -18,6 +18,7 @@ import numpy as np
 from . import device_staging as ds
 from .device_staging import BICUBIC, BILINEAR, BOX, LANCZOS, NEAREST, PRECISION_BITS, check_image, check_images, round_up  # noqa: F401
 from .jpeg_dct import PendingInputs
+from .jpeg_pixels import CoefficientImage
 
 FILTERS = (NEAREST, LANCZOS, BILINEAR, BICUBIC, BOX)
 
@@ -93,12 +94,16 @@ class PatchPlan(ds.StagedPlan):
     rectangle of each image that its window covers is staged: the descriptor's window is relative to that rectangle.
     `photometric` (optional): per image, the `PhotoParams` of data/ssd_photometric.py that dj_ssd_photometric applies to
     the staged rectangles before the resize; the records then travel as a fourth part behind the pixels.  Without them
-    there is no such part and the layout is the three-part one."""
+    there is no such part and the layout is the three-part one.  An item of `shapes` may be a `CoefficientImage` instead of
+    (height, width): its staged rectangle is then reconstructed on the GPU from the file's coefficients (`StagedPlan`),
+    whose parts lie behind all of these."""
     DESC_DTYPE = DESC_DTYPE
     photo_offset = None
 
     def __init__(self, shapes, geometries, out_height, out_width, photometric=None):
-        shapes = [(int(h), int(w)) for h, w in shapes]
+        items = list(shapes)
+        shapes = [(int(s.shape[0]), int(s.shape[1])) if isinstance(s, CoefficientImage) else (int(s[0]), int(s[1]))
+                  for s in items]
         geometries = [check_geometry(g) for g in geometries]
         if len(shapes) != len(geometries) or not shapes:
             raise ValueError("expected one geometry per image and at least one image")
@@ -140,11 +145,12 @@ class PatchPlan(ds.StagedPlan):
                 raise ValueError("expected one photometric record per image: %d records for %d images"
                                  % (len(self.photo), self.batch))
             parts.append(("photo", self.photo))
+        parts += self._plan_decode(items, self.rects, [(int(d["src_offset"]), int(d["src_stride"])) for d in self.desc])
         self._lay_out(parts)
 
     def _fill_pixels(self, src, images):
         for d, (ya, yb, xa, xb), img in zip(self.desc, self.rects, images):
-            if yb > ya:
+            if yb > ya and not isinstance(img, CoefficientImage):
                 o = int(d["src_offset"])
                 src[o:o + 3 * (xb - xa) * (yb - ya)].reshape(yb - ya, xb - xa, 3)[...] = img[ya:yb, xa:xb]
 
@@ -156,9 +162,10 @@ class PatchPlan(ds.StagedPlan):
         return self.part(blob, self.photo_offset, self.photo, self.photo.dtype)
 
     def launch(self, blob_host, blob_dev, out, scratch, stream=None):
-        """dj_ssd_photometric in place on the staged rectangles when the plan carries records, before dj_patch_resize
-        reads them into `out`."""
+        """dj_jpeg_pixels for the items that travel as coefficients, then dj_ssd_photometric in place on the staged
+        rectangles when the plan carries records, before dj_patch_resize reads them into `out`."""
         from .. import kernels
+        self.launch_decode(blob_host, blob_dev, scratch, stream)
         src_h, desc_h, pool_h = self.views(blob_host)
         src_d, desc_d, pool_d = self.views(blob_dev)
         if self.photo is not None:
@@ -172,8 +179,13 @@ def patch_resize_device(images, geometries, out_height, out_width, device=None, 
     `DevicePatchResize` keeps its own).  `photometric`: one `PhotoParams` per image, applied before the window is cut
     (`ssd_photometric_host`)."""
     images = check_images(images)
-    plan = PatchPlan([im.shape[:2] for im in images], geometries, out_height, out_width, photometric)
+    plan = PatchPlan(_plan_items(images), geometries, out_height, out_width, photometric)
     return ds.run_once(plan, images, device, out, stream)
+
+
+def _plan_items(images):
+    """What `PatchPlan` takes per image: the `CoefficientImage` itself, (height, width) of a decoded array."""
+    return [im if isinstance(im, CoefficientImage) else im.shape[:2] for im in images]
 
 
 class PendingPatchInputs(PendingInputs):
@@ -193,7 +205,7 @@ class PendingPatchInputs(PendingInputs):
             from .ssd_photometric import check_params
             self.photometric = [check_params(p) for p in photometric]
         # descriptors and taps are made where the batch is made (a generator's prefetch thread), not at upload time
-        self.plan = PatchPlan([im.shape[:2] for im in self.images], self.geometries, prep.out_height, prep.out_width,
+        self.plan = PatchPlan(_plan_items(self.images), self.geometries, prep.out_height, prep.out_width,
                               self.photometric)
         PendingInputs.__init__(self, prep, self.plan.out_shape)
 
@@ -206,9 +218,10 @@ class PendingPatchInputs(PendingInputs):
 
     def pixels(self):
         """The (B, out_height, out_width, 3) uint8 batch computed on the host (`ssd_photometric_host` where there are
-        records, then `patch_resize_host`, per image)."""
+        records, then `patch_resize_host`, per image; an item that travels as coefficients is `jpeg_pixels_host` of its
+        file first)."""
         p = self.prep
-        images = self.images
+        images = [im.pixels() if isinstance(im, CoefficientImage) else im for im in self.images]
         if self.photometric is not None:
             from .ssd_photometric import ssd_photometric_host
             images = [ssd_photometric_host(im, rec) for im, rec in zip(images, self.photometric)]
@@ -219,16 +232,17 @@ class PendingPatchInputs(PendingInputs):
 
 class DevicePatchResize(ds.ResidentBuffers):
     """Stands where the reference's SSD generator runs the geometric stages of its augmentation chain in numpy and cv2
-    and then saves each image as a JPEG and reads it back: the generator thread only decodes and plans
-    (`SSDDataAugmentation.plan`), the covered part of each image goes up once and both steps run on the GPU when the model
-    uploads the batch -- after the chain's photometric stage, when the plan drew one (`photometric`).  `quality` / `tables`
+    and then saves each image as a JPEG and reads it back: the generator thread decodes and plans
+    (`SSDDataAugmentation.plan`) -- or, handed `CoefficientImage`s, does not even decode: the files' coefficients go up and
+    dj_jpeg_pixels makes the staged pixels --, the covered part of each image goes up once and both steps run on the GPU
+    when the model uploads the batch -- after the chain's photometric stage, when the plan drew one (`photometric`).  `quality` / `tables`
     / `deconv` and the buffers as `ResidentBuffers` keeps them."""
 
-    def __init__(self, out_height=300, out_width=300, quality=75, tables=None, deconv=False):
+    def __init__(self, out_height=300, out_width=300, quality=75, tables=None, deconv=False, n_threads=None):
         self.out_height, self.out_width = int(out_height), int(out_width)
         if self.out_height < 1 or self.out_width < 1:
             raise ValueError("the output size must be positive")
-        ds.ResidentBuffers.__init__(self, quality, tables, deconv)
+        ds.ResidentBuffers.__init__(self, quality, tables, deconv, n_threads)
 
     def __call__(self, images, geometries, photometric=None):
         return PendingPatchInputs(self, images, geometries, photometric)

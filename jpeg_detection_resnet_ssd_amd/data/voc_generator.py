@@ -10,6 +10,12 @@ transform run on the GPU when the model uploads the batch.  A chain with a drawa
 (`SSDDataAugmentation(..., photometric_distortions=SSDPhotometricDistortions())`) is asked for that stage's draws too
 (`plan(..., return_photometric=True)`), and the records go to `device_prep(images, geometries, photometric=records)`: the
 stage then runs on the GPU on the staged pixels, before the window is cut.  Both paths leave bit-identical inputs.
+With `device_decode=True` as well, a file is not decoded here either: it is read as bytes, and when the in-tree reader
+calls it decodable (data/jpeg_pixels.py) it travels as a `CoefficientImage` whose height and width come from the header;
+worker threads entropy-decode it into the pinned staging buffer (as many as `device_prep` was built with:
+`DevicePatchResize(..., n_threads=)`) and dj_jpeg_pixels reconstructs the staged
+rectangle on the GPU, byte for byte what Pillow would have decoded.  Any other file (progressive, CMYK, ...) is decoded
+with Pillow as before, so a batch may mix the two.  Draws, boxes and dropped items do not depend on the switch.
 
 Differences from the reference: images are decoded with `convert("RGB")` (its `ConvertTo3Channels` lives in the
 photometric stage, which sees three channels here); the dataset is reshuffled with `np.random.permutation`
@@ -67,6 +73,17 @@ class DataGeneratorDCT(object):
         from PIL import Image
         with Image.open(filename) as image:
             return np.array(image.convert("RGB"), dtype=np.uint8)
+
+    @classmethod
+    def _read(cls, filename):
+        """The file as a `CoefficientImage` when the GPU can reconstruct its pixels, else decoded as `_decode` does."""
+        from .jpeg_pixels import CoefficientImage
+        with open(filename, "rb") as f:
+            data = f.read()
+        try:
+            return CoefficientImage(data)
+        except ValueError:              # not `decodable`, or no JPEG the reader can parse
+            return cls._decode(filename)
 
     def parse_xml(self, images_dirs, image_set_filenames, annotations_dirs=(), classes=VOC_CLASSES, include_classes='all',
                   exclude_truncated=False, exclude_difficult=False, ret=False, verbose=False):
@@ -131,18 +148,24 @@ class DataGeneratorDCT(object):
 
     def generate(self, batch_size=32, shuffle=True, transformations=(), label_encoder=None,
                  returns=('processed_images', 'encoded_labels'), keep_images_without_gt=False,
-                 degenerate_box_handling='remove', deconv=False, device_prep=None, n_threads=None):
+                 degenerate_box_handling='remove', deconv=False, device_prep=None, n_threads=None,
+                 device_decode=False):
         """Yields batches for ever; a pass that ends reshuffles (when `shuffle`) and starts over.  Per batch, as in the
         reference: an item without boxes, before or after its transformations, is dropped unless
         `keep_images_without_gt`; an item whose transformation gives up (returns None) is dropped; degenerate boxes are
         removed ('remove') or warned about ('warn').  Output order: processed_images, encoded_labels, processed_labels,
         filenames, image_ids, evaluation-neutral, inverse_transform, original_images, original_labels -- those named in
-        `returns`.  `device_prep`: see the module's docstring; a transformation without `plan` raises there."""
+        `returns`.  `device_prep`: see the module's docstring; a transformation without `plan` raises there.
+        `device_decode`: with `device_prep` only (ValueError otherwise): files the GPU can reconstruct are not decoded on
+        the host (images already in memory stay the arrays they are)."""
         if self.dataset_size == 0:
             raise ValueError("the dataset is empty: call parse_xml first")
         if degenerate_box_handling not in ('remove', 'warn'):
             raise ValueError("`degenerate_box_handling` must be 'remove' or 'warn'")
         transformations = list(transformations)
+        if device_decode and device_prep is None:
+            raise ValueError("device_decode needs device_prep: the coefficients are turned into pixels where the batch "
+                             "is staged for the GPU")
         if device_prep is not None:
             for transform in transformations:
                 if not hasattr(transform, 'plan'):
@@ -165,12 +188,16 @@ class DataGeneratorDCT(object):
             batch_filenames = list(self.filenames[window])
             if self.images is not None:
                 batch_X = list(self.images[window])
+            elif device_decode:
+                batch_X = [self._read(f) for f in batch_filenames]
             else:
                 batch_X = [self._decode(f) for f in batch_filenames]
             batch_y = deepcopy(self.labels[window]) if self.labels is not None else None
             batch_eval_neutral = list(self.eval_neutral[window]) if self.eval_neutral is not None else None
             batch_image_ids = list(self.image_ids[window])
-            batch_original_images = deepcopy(batch_X) if 'original_images' in returns else None
+            batch_original_images = None
+            if 'original_images' in returns:
+                batch_original_images = [x.pixels() if hasattr(x, 'pixels') else deepcopy(x) for x in batch_X]
             batch_original_labels = deepcopy(batch_y) if 'original_labels' in returns else None
             current += batch_size
 

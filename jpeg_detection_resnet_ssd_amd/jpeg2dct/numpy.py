@@ -19,6 +19,12 @@ class JpegInfo(ctypes.Structure):   # dj_jpeg_info
                 ("blocks_h", ctypes.c_int * 4), ("quant", (ctypes.c_int * 64) * 4), ("sof", ctypes.c_int)]
 
 
+class JpegDecodeInfo(ctypes.Structure):   # dj_jpeg_decode_info
+    _fields_ = [("base", JpegInfo), ("component_id", ctypes.c_int * 4), ("saw_jfif", ctypes.c_int),
+                ("saw_adobe", ctypes.c_int), ("adobe_transform", ctypes.c_int), ("precision", ctypes.c_int),
+                ("device_decodable", ctypes.c_int)]
+
+
 def _lib():
     global _LIB
     if _LIB is None:
@@ -37,6 +43,12 @@ def _lib():
         lib.dj_jpeg_decode_batch_f32.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_long),
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p] + [ctypes.c_int] * 5
+        lib.dj_jpeg_read_decode_info.restype = ctypes.c_int
+        lib.dj_jpeg_read_decode_info.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.POINTER(JpegDecodeInfo)]
+        lib.dj_jpeg_read_raw_batch.restype = ctypes.c_int
+        lib.dj_jpeg_read_raw_batch.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_long), ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_int]
         _LIB = lib
     return _LIB
 
@@ -52,6 +64,53 @@ def info(buf):
     inf = JpegInfo()
     _check(_lib().dj_jpeg_read_info(buf, len(buf), ctypes.byref(inf)))
     return inf
+
+
+def decode_info(buf):
+    """`info` plus what decides the colour space (component ids, JFIF / Adobe markers, precision) and the reader's verdict
+    `device_decodable` (include/dj_jpeg_decode.h) -> JpegDecodeInfo; ValueError for what the reader cannot parse."""
+    buf = bytes(buf)
+    inf = JpegDecodeInfo()
+    _check(_lib().dj_jpeg_read_decode_info(buf, len(buf), ctypes.byref(inf)))
+    return inf
+
+
+def default_threads():
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 1
+
+
+def read_raw_batch(buffers, out, plane_offsets, plane_capacity, n_threads=None):
+    """n JPEG byte strings -> their RAW (not de-quantised) int16 coefficient planes written into `out`, one caller-owned
+    C-contiguous uint8 array (e.g. the numpy view of a pinned staging buffer), by `n_threads` host threads with the GIL
+    released.  plane_offsets / plane_capacity: (n, 4) -- component c of file i goes to byte offset plane_offsets[i, c] and
+    may take plane_capacity[i, c] values (both checked against the file and against `out`).  -> (n,) int32 status, 0 or
+    negative per file: a file that fails leaves the others alone (`last_error()` has the first one's text)."""
+    bufs = [bytes(b) for b in buffers]
+    n = len(bufs)
+    if n == 0:
+        raise ValueError("expected at least one file")
+    if not (isinstance(out, _np.ndarray) and out.dtype == _np.uint8 and out.ndim == 1 and out.flags["C_CONTIGUOUS"]
+            and out.flags["WRITEABLE"]):
+        raise ValueError("out: expected a writable C-contiguous 1-D uint8 array")
+    offs = _np.ascontiguousarray(plane_offsets, dtype=_np.int64)
+    caps = _np.ascontiguousarray(plane_capacity, dtype=_np.int64)
+    if offs.shape != (n, 4) or caps.shape != (n, 4):
+        raise ValueError("plane_offsets / plane_capacity: expected shape (%d, 4)" % n)
+    arr = (ctypes.c_char_p * n)(*bufs)
+    sizes = (ctypes.c_long * n)(*[len(b) for b in bufs])
+    status = _np.zeros(n, dtype=_np.int32)
+    rc = _lib().dj_jpeg_read_raw_batch(arr, sizes, n, out.ctypes.data, out.size, offs.ctypes.data, caps.ctypes.data,
+                                       status.ctypes.data, int(n_threads if n_threads is not None else default_threads()))
+    if rc < 0:
+        _check(rc)
+    return status
+
+
+def last_error():
+    return _lib().dj_jpeg_last_error().decode()
 
 
 def loads(buf, normalized=True, channels=3):
@@ -91,10 +150,7 @@ def decode_batch(buffers, y_blocks, c_blocks, normalized=True, n_threads=None, o
     arr = (ctypes.c_char_p * n)(*bufs)
     sizes = (ctypes.c_long * n)(*[len(b) for b in bufs])
     if n_threads is None:
-        try:
-            n_threads = len(os.sched_getaffinity(0))
-        except AttributeError:
-            n_threads = os.cpu_count() or 1
+        n_threads = default_threads()
     _check(_lib().dj_jpeg_decode_batch_f32(arr, sizes, n, int(bool(normalized)), y.ctypes.data, cb.ctypes.data,
                                            cr.ctypes.data, yh, yw, ch, cw, int(n_threads)))
     return y, cb, cr

@@ -524,6 +524,27 @@ def ssd_photometric(src, desc_dev, desc_host, params_dev, params_host, stream=No
     return src
 
 
+# ---- JPEG pixels from entropy-decoded coefficients, into the staged rectangles ------------------------------------------------
+def jpeg_pixels(coef, desc_dev, desc_host, tables_dev, tables_host, dst, scratch, stream=None):
+    """dj_jpeg_pixels: `coef` the 1-D uint8 CUDA tensor holding the raw int16 coefficient planes, `desc_dev` the decode
+    descriptors' bytes on the device and `desc_host` the same as a numpy array of data/device_staging.py:DECODE_DTYPE,
+    `tables_dev` the quantisation tables' bytes on the device (1-D uint8) and `tables_host` the same as an int32 numpy
+    array (only its size is read), `dst` the 1-D uint8 CUDA tensor of staged pixels the rectangles are written into,
+    `scratch` a 1-D uint8 CUDA tensor holding the sample planes where the descriptors say.  `stream`: a HIP stream handle
+    (None: the current launch stream)."""
+    import numpy as np
+    from ._lib import JpegPixelsDesc
+    from .data.device_staging import DECODE_DTYPE
+    n = _check_staged(desc_host, DECODE_DTYPE, JpegPixelsDesc, desc_dev,
+                      ((coef, "coef"), (desc_dev, "desc_dev"), (tables_dev, "tables_dev"), (dst, "dst"), (scratch, "scratch")))
+    assert isinstance(tables_host, np.ndarray) and tables_host.dtype == np.int32, "tables_host: expected an int32 array"
+    assert tables_dev.numel() >= tables_host.nbytes, "tables_dev: smaller than the tables"
+    check(_L().dj_jpeg_pixels(ptr(coef), coef.numel(), ptr(desc_dev), desc_host.ctypes.data, n, ptr(tables_dev),
+                              tables_host.size, ptr(dst), dst.numel(), ptr(scratch), scratch.numel(),
+                              stream if stream is not None else _stream()), "dj_jpeg_pixels")
+    return dst
+
+
 # ---- Pascal-VOC evaluation: greedy matching, then cumulative counts / precision / recall / sampled AP -------------------------
 def _check_eval_tensor(t, name, dtype, numel):
     assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel, \

@@ -8,7 +8,8 @@ Differences, all forced by what is absent offline: the Pascal-VOC DataGeneratorD
 replaced by a synthetic JPEG-DCT generator with the same emission contract unless `DATASET_PATH` points at a Pascal-VOC
 tree in the reference's layout (VOC2007/ and, with --p07p12, VOC2012/, each with JPEGImages, Annotations and
 ImageSets/Main: then data/voc_generator.py reads it, augmented by data/ssd_augment.py as --crop / --no_crop select, on
-the host or, with `DJ_DEVICE_PREP=1`, planned on the host and run on the GPU) or `--generator module:factory` names a
+the host or, with `DJ_DEVICE_PREP=1`, planned on the host and run on the GPU; `DJ_DEVICE_DECODE=1` on top of that leaves
+the pixel half of JPEG decoding to the GPU too) or `--generator module:factory` names a
 user-supplied one; checkpoints are .npz name->array archives (h5py is not installed); `--weights` goes straight to
 `load_weights(by_name=True)` (the reference's preceding `load_model` only prints a summary).
 Multi-GPU (not in the reference: "no multi-GPU support for this part") = one process per GPU:
@@ -165,7 +166,15 @@ if os.environ.get("DATASET_PATH") and not args.generator:
         # opt-in: the generator decodes and plans, window + mirror + resize + JPEG transform run on the GPU at upload time
         # (tests/test_ssd_augment_gpu.py)
         from jpeg_detection_resnet_ssd_amd.data.patch_resize import DevicePatchResize
-        emit_kwargs["device_prep"] = DevicePatchResize(img_height, img_width, quality=75, deconv=deconv)
+        emit_kwargs["device_prep"] = DevicePatchResize(img_height, img_width, quality=75, deconv=deconv,
+                                                       n_threads=int(os.environ.get("DJ_DECODE_THREADS", "16")))
+        if os.environ.get("DJ_DEVICE_DECODE", "0") == "1":
+            # opt-in on top: files travel as entropy-decoded coefficients (read on DJ_DECODE_THREADS host threads, default
+            # 16) and dj_jpeg_pixels makes the staged pixels
+            # (tests/test_jpeg_pixels_gpu.py); files it does not cover are decoded with Pillow as before
+            emit_kwargs["device_decode"] = True
+    elif os.environ.get("DJ_DEVICE_DECODE", "0") == "1":
+        raise SystemExit("DJ_DEVICE_DECODE=1 needs DJ_DEVICE_PREP=1")
 train_generator = train_dataset.generate(batch_size=batch_size, shuffle=True, transformations=train_transformations,
                                          label_encoder=label_encoder,
                                          returns={"processed_images", "encoded_labels"},

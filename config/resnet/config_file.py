@@ -8,7 +8,8 @@ Data: ImageNet + jpeg2dct are absent, so by default the generators are synthetic
 (same emission contract as DCTGeneratorJPEG2DCT / DCTGeneratorJPEG2DCTDeconv, vgg_jpeg_keras/generators/generators.py:39-353).
 With `DJ_TRAIN_DIR`, `DJ_VAL_DIR` and `DJ_INDEX_FILE` all set, the DCT architectures read real images through
 jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators instead; `DJ_DEVICE_PREP=1` then moves resize, crop, flip and the
-JPEG transform of those images to the GPU.
+JPEG transform of those images to the GPU.  `prepare_testing_generator` (evaluate.py) reads `DJ_TEST_DIR`, or `DJ_VAL_DIR`
+without it, with `DJ_INDEX_FILE` in the same way, and yields synthetic batches otherwise.
 `prepare_horovod(hvd)` reproduces the reference's data-parallel scaling rules (:121-150) with `hvd` = the RCCL adapter
 of training.py."""
 from os import environ
@@ -23,12 +24,14 @@ from jpeg_detection_resnet_ssd_amd.keras.losses import categorical_crossentropy
 from jpeg_detection_resnet_ssd_amd.keras.metrics import top_k_categorical_accuracy
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
 from jpeg_detection_resnet_ssd_amd.keras.utils import Sequence
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.evaluation import Evaluator
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 
 
 def _top_k_accuracy(k):
     def _func(y_true, y_pred):
         return top_k_categorical_accuracy(y_true, y_pred, k)
+    _func._dj_metric = ("top_k", k)      # a validation / evaluation sweep counts it on the device, without calling it
     return _func
 
 
@@ -103,6 +106,7 @@ class TrainingConfiguration(object):
         self._horovod = None
         self._train_generator = None
         self._validation_generator = None
+        self._test_generator = None
         self._evaluator = None
 
     # -- callbacks -------------------------------------------------------------------------------
@@ -138,10 +142,26 @@ class TrainingConfiguration(object):
         pass
 
     def prepare_evaluator(self):
-        self._evaluator = None
+        self._evaluator = Evaluator()
 
     def prepare_testing_generator(self):
-        pass
+        """The generator evaluate.py sweeps: built like the validation generator (`scale=False`, no transformations).
+        Real images when `DJ_TEST_DIR` (or, without it, `DJ_VAL_DIR`) and `DJ_INDEX_FILE` are set and the architecture reads
+        DCT inputs, with `DJ_DEVICE_PREP=1` as in training; otherwise the synthetic batches the validation path uses."""
+        directory = environ.get("DJ_TEST_DIR") or environ.get("DJ_VAL_DIR")
+        index_file = environ.get("DJ_INDEX_FILE")
+        if directory and index_file and self.archi != "resnet_rgb":
+            from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (DCTGeneratorJPEG2DCT,
+                                                                                 DCTGeneratorJPEG2DCTDeconv)
+            cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
+            self.validation_directory, self.index_file = directory, index_file
+            self._test_generator = cls(directory, index_file, self._batch_size, scale=False,
+                                       device_prep=environ.get("DJ_DEVICE_PREP", "0") == "1")
+        elif self.archi == "resnet_rgb":
+            self._test_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
+        else:
+            self._test_generator = SyntheticDCTClassificationGenerator(self._batch_size, self.deconv, self.num_classes,
+                                                                       n_batches=8, seed=999983)
 
     def prepare_training_generators(self):
         rank = self.horovod.rank() if self.horovod is not None else 0
@@ -187,7 +207,7 @@ class TrainingConfiguration(object):
     horovod = property(lambda self: self._horovod)
     train_generator = property(lambda self: self._train_generator)
     validation_generator = property(lambda self: self._validation_generator)
-    test_generator = property(lambda self: None)
+    test_generator = property(lambda self: self._test_generator)
     evaluator = property(lambda self: self._evaluator)
 
     @property

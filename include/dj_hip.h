@@ -654,6 +654,24 @@ int dj_eval_rank(const int* rec_class, const int* rec_image, const float* rec_co
                  float* pred_conf, float* pred_boxes, int* seg_class, int* seg_image, int* seg_offsets, int* seg_ranks,
                  void* workspace, long workspace_bytes, void* stream);
 
+/* ---- Validation metrics of a classifier, accumulated over a whole pass of a generator (Model.evaluate_generator and the
+ * validation sweep of fit_generator; C/vgg_jpeg_keras/evaluation/evaluators.py:13-22, C/config/resnet/config_file.py:19-22).
+ * keras/metrics.py:classification_counts_host states the counting in numpy; the counts here equal it exactly.
+ * y_true / probs: contiguous float32 [rows][C] on the device.  Per row t = np.argmax(y_true[row]) (the first maximum, a NaN
+ * counts as the maximum) and p_t = probs[row][t].  Entry q of ks_host (n_k <= 8 ints on the HOST, read during the call: they
+ * travel in the kernel arguments) with k >= 1 is tf.nn.in_top_k, which Keras 2.2.4's top_k_categorical_accuracy calls: a hit
+ * iff p_t is finite and fewer than k classes have a probability > p_t, so classes tied with the target all count as in the
+ * top k and a NaN elsewhere in the row is not counted; k == 0 is categorical_accuracy: a hit iff np.argmax(probs[row]) == t.
+ * counts [1 + n_k] int64: [0] += rows, [1 + q] += hits of entry q.  acc [2] float64: with loss_mean (device, the mean loss
+ * of the batch as the loss entry points leave it; may be NULL) acc[0] += loss_weight * (double)loss_mean[0], the product
+ * rounded before the sum, and acc[1] += loss_weight.  With rows == 0, or y_true / probs NULL, only the loss is accumulated.
+ * The caller zeroes acc and counts once per pass.  One launch, no synchronisation; hit counts are added as integers and the
+ * loss term by one thread, so the result does not depend on the grid, and successive calls on one stream add in call
+ * order.  Refused before any launch: n_k outside 0..8, a k outside 0..C (a loss-only call with rows == 0 and C <= 0 states
+ * no C: there only a negative k), rows < 0, C <= 0 with rows > 0, acc or counts NULL. ---- */
+int dj_eval_accumulate(const float* y_true, const float* probs, long rows, int C, const int* ks_host, int n_k,
+                       const float* loss_mean, double loss_weight, double* acc, long long* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

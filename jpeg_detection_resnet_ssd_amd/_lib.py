@@ -198,6 +198,7 @@ SIGNATURES = {
     "dj_eval_rank_workspace_bytes": (c_long, [c_long, c_int]),
     "dj_eval_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "dj_eval_accumulate": (c_int, [FP, FP, c_long, c_int, c_void_p, c_int, FP, c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 

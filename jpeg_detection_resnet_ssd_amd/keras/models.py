@@ -553,6 +553,46 @@ class Model(object):
             return [np.concatenate([c[j] for c in chunks], axis=0) for j in range(len(chunks[0]))]
         return np.concatenate(chunks, axis=0)
 
+    # ---- evaluation -------------------------------------------------------------------
+    @property
+    def metrics_names(self):
+        """['loss'] followed by the log names of the compiled metrics (`_func`, `_func_1`, `acc`, ...)."""
+        from .metrics import metric_entries
+        return ["loss"] + [name for name, _ in metric_entries(self.metrics)]
+
+    def evaluate_generator(self, generator, steps=None, max_queue_size=10, workers=1, use_multiprocessing=False, verbose=0):
+        """Keras `evaluate_generator` (classification_part/vgg_jpeg_keras/evaluation/evaluators.py:22): `steps` batches of
+        `generator` (all of a `Sequence` when None) -> the loss, averaged over the batches weighted by their sizes plus the
+        regularisation penalty, as a scalar when the model was compiled without metrics, else [loss, metric, ...] in
+        `metrics_names` order.  Loss and hit counts are accumulated on the device (dj_eval_accumulate, one launch behind each
+        forward pass) and downloaded once, when the pass ends.  On a data-parallel model every rank evaluates what its own
+        generator yields and the values returned are the local rank's: nothing is averaged across ranks here."""
+        if steps is None:
+            if hasattr(generator, "__len__"):     # keras.utils.Sequence
+                steps = len(generator)
+            else:
+                raise ValueError("`steps=None` is only valid for a generator based on the `keras.utils.Sequence`"
+                                 " class. Please specify `steps` or use the `keras.utils.Sequence` class.")
+        import itertools
+        steps = int(steps)
+        it = itertools.islice(iter(generator), steps)     # the background thread stops where the pass does
+        feeder = _Prefetcher(it, max_queue_size) if workers and workers > 0 else None
+        sweep = _EvalSweep(self, size_weighted=True)
+        t0 = time.time()
+        try:
+            for _ in range(steps):
+                batch = feeder.get() if feeder is not None else next(it)
+                sweep.add(batch[0], batch[1])
+        finally:
+            if feeder is not None:
+                feeder.close()
+        values = sweep.finish()
+        out = [values[name] for name in self.metrics_names]
+        if verbose:
+            print("%d/%d - %.0fs - %s" % (steps, steps, time.time() - t0,
+                                          " - ".join("%s: %.4f" % (n, v) for n, v in zip(self.metrics_names, out))))
+        return out[0] if len(out) == 1 else out
+
     # ---- training loop ----------------------------------------------------------------
     def fit_generator(self, generator, steps_per_epoch=None, epochs=1, verbose=1, callbacks=None,
                       validation_data=None, validation_steps=None, class_weight=None, max_queue_size=10, workers=1,
@@ -605,15 +645,17 @@ class Model(object):
             for mk, mv in run_metrics.items():
                 logs[mk] = mv / max(1, step + 1)
             if validation_data is not None:
-                vl, nv = 0.0, 0
+                # val_loss: the plain mean over the batches of data loss + penalty (every batch weighs 1); the metrics are
+                # hits / rows.  One download for the whole sweep.
+                sweep = _EvalSweep(self, size_weighted=False)
                 if val_it is not None:
                     for _ in range(int(validation_steps)):
                         vb = next(val_it)
-                        vl += self.test_on_batch(vb[0], vb[1])
-                        nv += 1
+                        sweep.add(vb[0], vb[1])
                 else:
-                    vl, nv = self.test_on_batch(validation_data[0], validation_data[1]), 1
-                logs["val_loss"] = vl / max(1, nv)
+                    sweep.add(validation_data[0], validation_data[1])
+                for mk, mv in sweep.finish().items():
+                    logs["val_" + mk] = mv
             if self.dist is not None:
                 logs = self.dist.average_metrics(logs)
             if verbose and rank0:
@@ -628,6 +670,86 @@ class Model(object):
         for cb in cb_list:
             cb.on_train_end()
         return history
+
+
+class _EvalSweep(object):
+    """One pass of a model over evaluation batches whose loss and metrics stay on the device until the pass ends.
+    Per batch: the inference plan's forward pass and one dj_eval_accumulate behind it on the same stream, which adds
+    weight * (the batch's mean loss) and weight to `acc` and, for a 2-D float32 probability output, the row count and the
+    hits of every metric the kernel can take (keras/metrics.py:device_metric_k) to `counts`.  `size_weighted`: the weight
+    is the batch size (evaluate_generator), else 1 (fit_generator's val_loss, a plain mean over batches).  Any other
+    metric callable is evaluated per batch on the device tensors, as Model._metric_values does -- one host sync each --
+    and averaged weighted by batch size.  The regularisation penalty does not change during a pass: it is computed once,
+    in `finish`, which makes the pass's only download of the accumulators."""
+
+    def __init__(self, model, size_weighted):
+        from .metrics import metric_entries
+        self.model, self.size_weighted = model, size_weighted
+        self.entries = metric_entries(model.metrics)
+        self.acc = None       # set up by the first batch: its plan tells whether the output can be classified on the device
+
+    def _setup(self, plan):
+        from .metrics import categorical_accuracy, device_metric_k
+        buf = plan.outputs[0].buf
+        classify = buf.dim() == 2 and buf.dtype == torch.float32 and buf.is_contiguous()
+        c = int(buf.shape[-1])
+        ks, self.slots, self.per_batch = [], {}, []
+        for name, m in self.entries:
+            k = device_metric_k(m) if classify else None
+            if k is not None:
+                k = min(k, c)                       # fewer than k classes above the target: the same for every k >= C
+                if k not in ks and len(ks) == 8:    # the kernel takes 8 entries per launch
+                    k = None
+            if k is None:
+                self.per_batch.append((name, m if callable(m) else categorical_accuracy))
+            else:
+                if k not in ks:
+                    ks.append(k)
+                self.slots[name] = 1 + ks.index(k)
+        self.ks = np.asarray(ks, dtype=np.int32)
+        self.classify = classify and len(ks) > 0
+        self.acc = torch.zeros(2, dtype=torch.float64, device=buf.device)
+        self.counts = torch.zeros(1 + len(ks), dtype=torch.int64, device=buf.device)
+        self.host_sums, self.host_rows = {name: 0.0 for name, _ in self.per_batch}, 0
+
+    def add(self, x, y):
+        from .. import kernels
+        model = self.model
+        b = model._as_list(x)[0].shape[0]
+        plan = model._plan(b, False, True)
+        model._upload(plan, x, y)
+        plan.run_forward()
+        if self.acc is None:
+            self._setup(plan)
+        probs = plan.outputs[0].buf
+        kernels.eval_accumulate(plan.y_true if self.classify else None, probs if self.classify else None, self.ks,
+                                plan.loss_out, float(b) if self.size_weighted else 1.0, self.acc, self.counts)
+        for name, m in self.per_batch:
+            self.host_sums[name] += b * float(m(plan.y_true, probs))
+        self.host_rows += b
+
+    def _download(self):
+        """The accumulators as one float64 host array [loss sum, weight sum, rows, hits...] (counts are exact in a double up
+        to 2^53): the one device-to-host copy of a pass."""
+        return torch.cat([self.acc, self.counts.to(torch.float64)]).cpu().numpy()
+
+    def finish(self):
+        """-> {'loss': ..., '<metric name>': ...} in the order of Model.metrics_names."""
+        out = {}
+        if self.acc is None:      # no batch at all
+            out["loss"] = float("nan")
+            for name, _ in self.entries:
+                out[name] = float("nan")
+            return out
+        host = self._download()
+        out["loss"] = float(host[0]) / float(host[1]) + self.model._reg_penalty()
+        rows = float(host[2])
+        for name, _ in self.entries:
+            if name in self.slots:
+                out[name] = float(host[2 + self.slots[name]]) / rows if rows else 0.0
+            else:
+                out[name] = self.host_sums[name] / self.host_rows if self.host_rows else 0.0
+        return out
 
 
 class _Prefetcher(object):

@@ -647,3 +647,31 @@ def eval_rank(records, n_classes, n_images, counters, out, workspace):
                             ptr(out["pred_boxes"]), ptr(out["seg_class"]), ptr(out["seg_image"]), ptr(out["seg_offsets"]),
                             ptr(out["seg_ranks"]), ptr(workspace), workspace.numel(), _stream()), "dj_eval_rank")
     return out
+
+
+# ---- validation metrics of a classifier, accumulated on the device over a pass of a generator ----------------------------------
+def eval_accumulate(y_true, probs, ks, loss_mean, loss_weight, acc, counts):
+    """dj_eval_accumulate: add one batch to the accumulators of a sweep.  `y_true` / `probs`: contiguous float32 CUDA
+    tensors [rows][C], or both None (only the loss is accumulated); `ks`: a contiguous int32 numpy array of at most 8
+    entries on the host (k >= 1: top-k accuracy as tf.nn.in_top_k counts it, 0: categorical accuracy); `loss_mean`: a
+    float32 CUDA tensor whose first element is the batch's mean loss, or None; `acc`: float64 CUDA tensor [2] receiving
+    (loss_weight * loss, loss_weight); `counts`: int64 CUDA tensor [1 + len(ks)] receiving (rows, hits per entry).  One launch, no
+    synchronisation."""
+    import numpy as np
+    assert isinstance(ks, np.ndarray) and ks.dtype == np.int32 and ks.ndim == 1 and ks.flags.c_contiguous, \
+        "ks: expected a contiguous int32 array on the host"
+    rows, c = 0, 0
+    if y_true is not None or probs is not None:
+        assert y_true is not None and probs is not None and probs.dim() == 2 and y_true.shape == probs.shape, \
+            "y_true / probs: expected two [rows][C] tensors of one shape"
+        rows, c = int(probs.shape[0]), int(probs.shape[1])
+        _check_eval_tensor(y_true, "y_true", torch.float32, rows * c)
+        _check_eval_tensor(probs, "probs", torch.float32, rows * c)
+    if loss_mean is not None:
+        assert loss_mean.is_cuda and loss_mean.dtype == torch.float32 and loss_mean.numel() >= 1, \
+            "loss_mean: expected a float32 CUDA tensor"
+    _check_eval_tensor(acc, "acc", torch.float64, 2)
+    _check_eval_tensor(counts, "counts", torch.int64, 1 + ks.size)
+    check(_L().dj_eval_accumulate(ptr(y_true), ptr(probs), rows, c, ks.ctypes.data, int(ks.size), ptr(loss_mean),
+                                  float(loss_weight), ptr(acc), ptr(counts), _stream()), "dj_eval_accumulate")
+    return acc, counts

@@ -183,6 +183,12 @@ int dj_conv2d_nhwc_fwd_bn(const dj_conv2d_desc* d, const float* x, const float* 
  * launcher pick the branch-free buffer-load kernel whenever its alignment preconditions hold. */
 void dj_set_fast_path(int enable);
 
+/* Debug/test switch: 0 sends the split-bf16 (float32x3 / float32x6) convolutions with taps, padding, stride or dilation
+ * to the kernels that redo their gather arithmetic every K-step, 1 (default) lets the launcher pick the variants that
+ * cache per-tap row offsets (forward, input gradient) or walk the pixel incrementally (weight gradient).  The twins sum
+ * the same products in the same order: their results are bit-equal. */
+void dj_set_gather_variants(int enable);
+
 /* Arithmetic of the implicit-GEMM kernels: 0 = fp32 (default; what every parity claim at 1e-3 refers to): fp32 tensors,
  * fp32 results, from whichever of two kernel families the tuning table names for a geometry -- v_mfma_f32_32x32x2_f32, or
  * the split-bf16 kernels of mode 4 (measured against the fp64 oracle the two are equally far from it, 1.4e-7 .. 4.6e-7

@@ -134,6 +134,7 @@ SIGNATURES = {
     "dj_conv2d_nhwc_fwd_bn": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, c_int, FP, c_int, FP, FP, FP, c_int,
                                       POINTER(BnTrain), c_void_p]),
     "dj_set_fast_path": (None, [c_int]),
+    "dj_set_gather_variants": (None, [c_int]),
     "dj_set_compute_mode": (c_int, [c_int]),
     "dj_set_thread_compute_mode": (c_int, [c_int]),
     "dj_get_compute_mode": (c_int, []),

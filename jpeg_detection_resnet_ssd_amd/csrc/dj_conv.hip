@@ -22,6 +22,8 @@ extern "C" int dj_abi_version(void) { return DJ_ABI_VERSION; }
 // test switch: atomic, read once per launch
 std::atomic<bool> g_dj_allow_fast{true};
 extern "C" void dj_set_fast_path(int enable) { g_dj_allow_fast.store(enable != 0, std::memory_order_relaxed); }
+std::atomic<bool> g_dj_gather_variants{true};
+extern "C" void dj_set_gather_variants(int enable) { g_dj_gather_variants.store(enable != 0, std::memory_order_relaxed); }
 
 // Arithmetic mode.  0: fp32 MFMA everywhere (default).  1: forward GEMMs round their operands to fp16, gradient GEMMs
 // (dgrad, wgrad) to bf16 (gradients need the exponent range); 2: bf16 everywhere; 3 ("float32x3"): fp32 tensors, every

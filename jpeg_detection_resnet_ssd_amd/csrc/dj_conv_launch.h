@@ -156,6 +156,9 @@ static int launch_k2(const DjIgemmParams& p, int splits, hipStream_t s, int fast
 }
 
 extern std::atomic<bool> g_dj_allow_fast;   // dj_conv.hip
+// dj_set_gather_variants (dj_conv.hip): false sends the split-bf16 launches that would take the tap-cache / pixel-walk
+// variants (NP 2 / 3 of dj_igemm_h16.h) to their plain twins
+extern std::atomic<bool> g_dj_gather_variants;
 
 // 0: fp32 results (default; fp32 MFMA or split-bf16 kernel per tuning entry), 5: fp32 MFMA only.  1: forward GEMMs round
 // their operands to fp16, gradient GEMMs (dgrad, wgrad) to bf16 (gradients need the exponent range); 2: bf16 everywhere;

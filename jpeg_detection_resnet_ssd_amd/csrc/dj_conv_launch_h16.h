@@ -43,6 +43,22 @@ static int launch_h16_kernel(int smem_bytes, const DjIgemmParams& p, int splits,
     if (!np_off && p.KH == 1 && p.KW == 1 && p.pT == 0 && p.pL == 0 && same_grid)
       return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 1>(smem_bytes, p, splits, s);
   }
+  // split-bf16 modes, every other geometry (taps, padding, stride, dilation): the weight gradient walks its pixel
+  // incrementally when a tile lies under one filter tap (NP 3), forward and input gradient keep the row offsets of the
+  // current tap (NP 2).  DJ_NO_NP=1 / DJ_NO_WALK=1 / DJ_NO_TAPCACHE=1 and dj_set_gather_variants(0) fall back to NP 0.
+  if constexpr (PRO != 3 && PREC >= 3) {
+    static const bool np_off = getenv("DJ_NO_NP") != nullptr;
+    if (!np_off && g_dj_gather_variants.load(std::memory_order_relaxed)) {
+      if constexpr (AM == 2) {
+        static const bool walk_off = getenv("DJ_NO_WALK") != nullptr;
+        if (!walk_off && p.srcC % BM == 0)
+          return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 3>(smem_bytes, p, splits, s);
+      } else {
+        static const bool ht_off = getenv("DJ_NO_TAPCACHE") != nullptr;
+        if (!ht_off) return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 2>(smem_bytes, p, splits, s);
+      }
+    }
+  }
   return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 0>(smem_bytes, p, splits, s);
 }
 

@@ -52,6 +52,7 @@
 #pragma once
 #include "dj_igemm.h"
 #include "dj_igemm_fast.h"
+#include "dj_walk.h"
 
 typedef short dj_tr4 __attribute__((__vector_size__(4 * sizeof(short))));   // what the transposing read returns
 typedef short dj_s16x8 __attribute__((ext_vector_type(8)));
@@ -161,9 +162,24 @@ __device__ __forceinline__ void dj_split_store3(short* dst, f32x4 v, int lo_off)
 //     this for the fp32 kernels (NP 1 of dj_igemm_fast.h); here the counters say the kernels are bound by instruction ISSUE
 //     (rocprofv3, 1x1 256->1024 @38x38 forward: instructions issuing in 83 % of a SIMD's cycles, matrix pipe busy 18 %, 37 %
 //     of a wave's life waiting for data), and two thirds of the convolutions of a bottleneck block are 1x1.
+//     2 = forward / input gradient with taps or padding (PRO 0 / 1): a row's byte offset under the CURRENT filter tap -- or
+//     0x80000000 where the tap leaves the image, which stays out of range whatever channel offset is added -- is kept in a
+//     register (a_tap) with the validity bits of the tap (tap_valid) and recomputed only when the prefetch moves on to the
+//     next tap: a wave-uniform branch taken once per in_c / BK K-steps.  The other K-steps add the channel position and
+//     nothing else.  The state is advanced at the end of issue_loads, so with PF 2 it follows the issue order as t_c0 does.
+//     3 = weight gradient with taps, padding, stride or dilation when in_c is a multiple of BM: the tile's BM rows lie under
+//     ONE filter tap and a thread's pixel moves by BK pixels every K-step.  The pixel is decomposed once (dj_walk.h);
+//     afterwards its coordinates and the byte offset of the tapped input pixel advance by wave-uniform constants with two
+//     carries.  No float reciprocals and no 32-bit multiplies in the K-step; a thread's chunks are 4 * ACG channels apart
+//     (constant offsets of the loads).  A tapped pixel in the padding is zeroed AFTER the prologue (store_a), as under NP 0.
+//     With six MFMAs per product a K-step of a 128x128 tile is 768 matrix-pipe cycles: the ~60 vector instructions per
+//     K-step the NP 0 weight gradient spends on addresses, a dozen of them quarter rate, load the vector pipe about as
+//     heavily as the MFMAs load the matrix pipe.  Instantiated for PREC 3 / 4 (dj_conv_launch_h16.h).
 template <int BM, int BN, int AM, int BMD, int PRO, int PREC, int BK = 32, int PF = 1, int EPI = 0, int AT = 0, int BT = 0, int NP = 0>
 __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p) {
   static_assert(NP == 0 || PRO != 3, "NP: not with the residual-add prologue (which keeps row indices of its own)");
+  static_assert(NP != 2 || AM != 2, "NP 2 (per-tap offsets) is for the k-contiguous A operand");
+  static_assert(NP != 3 || AM == 2, "NP 3 (pixel walk) is for the weight gradient's gathered operand");
   static_assert(EPI == 0 || (AM == 1 && BMD == 1), "BatchNormalization backward statistics: input-gradient GEMM only");
   static_assert(EPI != 2 || (PRO == 0 && AT == 0 && BT == 0), "masked accumulate: fp32 tensors, no prologue");
   static_assert(PREC < 3 || (AT == 0 && BT == 0), "float32x3 / float32x6: fp32 tensors");
@@ -265,13 +281,27 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
         a2_sh[i] = dj_buf_ld4(rT, a2_ok[i] ? (unsigned)a2_c[i] * 4u : DJ_OOB);
       }
       row_valid |= a2_ok[i] ? (1u << i) : 0u;
-      if (NP) a2_c[i] = a2_ok[i] ? a2_c[i] * EA : (int)0x80000000;   // byte offset of the chunk inside its pixel
+      if (NP == 1) a2_c[i] = a2_ok[i] ? a2_c[i] * EA : (int)0x80000000;   // byte offset of the chunk inside its pixel
     }
   }
   // NP, weight gradient: byte offset of this thread's pixel row (pixel kbeg + ar0 of the first K-step), advanced per K-step;
   // a pixel past the chunk reads other (finite) rows of x or nothing and meets a zero dy row
-  int np_row = (NP && AM == 2) ? (kbeg + ar0) * p.ldsrc * EA : 0;
+  int np_row = (NP == 1 && AM == 2) ? (kbeg + ar0) * p.ldsrc * EA : 0;
   const int np_step = BK * p.ldsrc * EA;
+  // NP 3: this thread's output pixel, its index and the byte offset of its first chunk at the tapped input pixel
+  // (dj_walk.h); the tile lies under the tap (walk_dh, walk_dw)
+  const DjWalkGeom walk_g{p.rowH, p.rowW, p.srcH, p.srcW, p.sH, p.sW, p.ldsrc * EA};
+  DjWalkStep walk_s{};
+  DjWalkPos walk{};
+  int walk_dh = 0, walk_dw = 0;
+  if (NP == 3) {
+    const int tap = m0 / p.srcC, cb = m0 - tap * p.srcC;
+    const int kh = tap / p.KW, kw = tap - kh * p.KW;
+    walk_dh = kh * p.dH - p.pT;
+    walk_dw = kw * p.dW - p.pL;
+    walk_s = dj_walk_step(walk_g, BK);
+    walk = dj_walk_init(walk_g, kbeg + ar0, walk_dh, walk_dw, (cb + 4 * ac) * EA);
+  }
   int b_off[NB];
   bool b_ok[NB];
   if (BMD == 0) {
@@ -297,6 +327,26 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
     t_kh = t_tap / p.KW;
     t_kw = t_tap - t_kh * p.KW;
   }
+
+  // NP 2: per-row offsets under the tap the NEXT issue_loads will read
+  int a_tap[NP == 2 ? NA : 1];
+  unsigned tap_valid = 0;
+  auto recompute_tap = [&]() {
+    if (NP == 2) {
+      const int dh = t_kh * p.dH, dw = t_kw * p.dW;
+      const int tapdelta = (AM == 0) ? (dh * p.srcW + dw) * p.ldsrc * EA : -(dh * p.srcW + dw) * p.ldsrc * EA;
+      tap_valid = 0;
+#pragma unroll
+      for (int j = 0; j < NA; ++j) {
+        const int h = (AM == 0) ? a_rh[j] + dh : a_rh[j] - dh;
+        const int w = (AM == 0) ? a_rw[j] + dw : a_rw[j] - dw;
+        const bool ok = ((unsigned)h < (unsigned)p.srcH) & ((unsigned)w < (unsigned)p.srcW);
+        a_tap[j] = ok ? a_off[j] + tapdelta : (int)0x80000000;   // stays out of range with any channel offset added
+        tap_valid |= ok ? (1u << j) : 0u;
+      }
+    }
+  };
+  recompute_tap();
 
   // one K-step's operands between the buffer loads and the LDS stores
   struct Regs {
@@ -350,6 +400,12 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
           ra2[j] = dj_buf_ldraw<AT>(rA2, ok ? (__umul24(m, (unsigned)p.ldsrc2) + cb) * (unsigned)EA : DJ_OOB);
           a_valid |= ok ? (1u << j) : 0u;
         }
+      } else if (NP == 2) {
+        // (the prefetch past the last K-step, never consumed: rows of the tap go out of range, the others to offset 0)
+        a_valid = tap_valid;
+        const unsigned uc = live ? (unsigned)(t_c0 * EA) : 0x80000000u;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) ra[j] = dj_buf_ldraw<AT>(rA, (unsigned)a_tap[j] + uc);
       } else if (NP) {
         // the prefetch past the last K-step (never consumed) is sent out of range by the wave-uniform part of the offset:
         // on these short-K launches one wasted K-step of loads is an eighth of the traffic
@@ -367,6 +423,15 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
         a_valid |= ok ? (1u << j) : 0u;
       }
       }
+    } else if (NP == 3) {
+      // 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate): coordinates and strides are far below 2^23
+      const int ih = __mul24(walk.oh, p.sH) + walk_dh, iw = __mul24(walk.ow, p.sW) + walk_dw;
+      const bool ok = live & dj_walk_inside(walk_g, walk, ih, iw, kend);
+      const unsigned voff = ok ? (unsigned)walk.off : 0x80000000u;   // stays out of range with the chunk offsets added
+      a_valid = ok ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+      for (int i = 0; i < NA; ++i) ra[i] = dj_buf_ldraw<AT>(rA, voff + (unsigned)(4 * ACG * EA * i));
+      dj_walk_advance(walk_g, walk_s, walk);
     } else if (NP) {
       a_valid = row_valid;
       const int urow = live ? np_row : (int)0x80000000;
@@ -419,6 +484,7 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
       const int wrap2 = (t_kw >= p.KW) ? 1 : 0;
       t_kw = wrap2 ? 0 : t_kw;
       t_kh += wrap2;
+      if (NP == 2 && wrap) recompute_tap();   // wave-uniform: the next K-step starts a new tap
     }
   };
 
@@ -439,9 +505,9 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
         f32x4 sc = (AM == 2) ? a2_sc[j] : psc, sh = (AM == 2) ? a2_sh[j] : psh;
         v = v * sc + sh;
         if (PRO == 3) v += dj_raw_to_f32<AT>(ra2[j]) * psc2 + psh2;
-        // (NP weight gradient: nothing to zero -- a chunk past M has zero scale AND shift, a pixel past the chunk meets a
-        // zero dy row)
-        bool ok = (NP && AM == 2) ? true : (bool)((a_valid >> j) & 1u);
+        // (NP 1 weight gradient: nothing to zero -- a chunk past M has zero scale AND shift, a pixel past the chunk meets a
+        // zero dy row.  NP 3: a tapped pixel in the padding arrived as zeros and the shift made it non-zero.)
+        bool ok = (NP == 1 && AM == 2) ? true : (bool)((a_valid >> j) & 1u);
         const float lo = ok ? relu_floor : 0.f, hi = ok ? INFINITY : 0.f;   // ReLU + out-of-bounds zero: one v_med3
         v.x = __builtin_amdgcn_fmed3f(v.x, lo, hi);
         v.y = __builtin_amdgcn_fmed3f(v.y, lo, hi);

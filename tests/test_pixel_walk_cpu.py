@@ -1,0 +1,27 @@
+"""CPU: the incremental pixel walk of the split-bf16 weight gradient (csrc/dj_walk.h, NP 3 of dj_igemm_h16.h) gives,
+for every thread row and every K-step of every K chunk, exactly the (in-bounds flag, byte offset) of the direct pixel
+decomposition.  tests/pixel_walk_check.cpp walks the grid (maps 1x1 .. 19x19, strides 1 / 2, dilation 1 / 6, 'same' and
+'valid' padding, K-steps of 16 and 32, chunks that end mid-row and mid-image, batch 1 .. 3); it is built here as a
+stand-alone program with the address and undefined-behaviour sanitizers and run directly."""
+import os
+import re
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_pixel_walk_equals_direct_decomposition(tmp_path):
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "pixel_walk_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", os.path.join(ROOT, "jpeg_detection_resnet_ssd_amd", "csrc"),
+           os.path.join(ROOT, "tests", "pixel_walk_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"pixel walk: (\d+) launches, (\d+) offsets equal", r.stdout)
+    assert m, r.stdout + r.stderr
+    assert int(m.group(1)) >= 500 and int(m.group(2)) >= 1000000

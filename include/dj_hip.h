@@ -183,10 +183,11 @@ int dj_conv2d_nhwc_fwd_bn(const dj_conv2d_desc* d, const float* x, const float* 
  * launcher pick the branch-free buffer-load kernel whenever its alignment preconditions hold. */
 void dj_set_fast_path(int enable);
 
-/* Debug/test switch: 0 sends the split-bf16 (float32x3 / float32x6) convolutions with taps, padding, stride or dilation
- * to the kernels that redo their gather arithmetic every K-step, 1 (default) lets the launcher pick the variants that
- * cache per-tap row offsets (forward, input gradient) or walk the pixel incrementally (weight gradient).  The twins sum
- * the same products in the same order: their results are bit-equal. */
+/* Debug/test switch: 0 sends the convolutions with taps, padding, stride or dilation -- of both branch-free kernel
+ * families, fp32 MFMA and split-bf16 (float32x3 / float32x6) -- to the kernels that redo their gather arithmetic every
+ * K-step, 1 (default) lets the launcher pick the variants that cache per-tap row offsets (forward, input gradient) or
+ * walk the pixel incrementally (weight gradient).  The twins sum the same products in the same order: their results are
+ * bit-equal.  The bounds-free variant of the unpadded 1x1 convolutions is not behind this switch. */
 void dj_set_gather_variants(int enable);
 
 /* Arithmetic of the implicit-GEMM kernels: 0 = fp32 (default; what every parity claim at 1e-3 refers to): fp32 tensors,

@@ -56,17 +56,17 @@ static int launch_kernel(KernT kern, int smem_bytes, int bm, int bn, const DjIge
 
 // One launch site per kernel instantiation; an input-gradient launch that asks for BatchNormalization backward statistics
 // (p.bnb_z) takes the EPI = 1 twin of the same variant, one that asks for the masked accumulate (p.mask_x) the EPI = 2 twin.
-template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE, int PREC, int KS, int NP>
+template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE, int KS, int NP>
 static int launch_fast(int smem_bytes, const DjIgemmParams& p, int splits, hipStream_t s, int threads = 256) {
   if constexpr (AM == 1 && BMD == 1 && PRO == 0) {   // (the input-gradient GEMM has no prologue)
     if (p.bnb_z) {
       static std::atomic<bool> done1{false};
-      return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 1>, smem_bytes, BM, BN, p,
+      return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, KS, NP, 1>, smem_bytes, BM, BN, p,
                            splits, s, &done1, threads);
     }
     if (p.mask_x) {
       static std::atomic<bool> done2{false};
-      return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 2>, smem_bytes, BM, BN, p,
+      return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, KS, NP, 2>, smem_bytes, BM, BN, p,
                            splits, s, &done2, threads);
     }
   }
@@ -75,52 +75,58 @@ static int launch_fast(int smem_bytes, const DjIgemmParams& p, int splits, hipSt
     return DJ_ERR_ARG;
   }
   static std::atomic<bool> done0{false};
-  return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, PREC, KS, NP, 0>, smem_bytes, BM, BN, p, splits,
+  return launch_kernel(dj_igemm_fast_kernel<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, KS, NP, 0>, smem_bytes, BM, BN, p, splits,
                        s, &done0, threads);
 }
 
-// fast = 0: generic kernel; 1: branch-free kernel; 2: branch-free kernel with the affine prologue
+extern std::atomic<bool> g_dj_allow_fast;   // dj_conv.hip
+// dj_set_gather_variants (dj_conv.hip): false sends the launches of BOTH kernel families that would take the tap-cache /
+// pixel-walk variants (NP 2 / 3) to their plain twins (NP 0); the bounds-free 1x1 variant (NP 1) is outside the switch
+extern std::atomic<bool> g_dj_gather_variants;
+
+// The gather variant (NP of dj_igemm_fast.h / dj_igemm_h16.h) of a branch-free launch: GEMM role `am`, tile rows `bm`,
+// prologue `pro`.  np23: whether the caller has the NP 2 / 3 instantiations at all.
+//   1: 1x1 kernel without padding -- for the weight gradient also stride 1, input pixel == output pixel
+//   3: weight gradient with taps / padding / stride whose tiles lie under one filter tap each (incremental pixel walk)
+//   2: forward / input gradient with taps / padding (row offsets of the current tap cached across its K-steps)
+//   0: everything else, the residual-add prologue, and what the switches turn off: DJ_NO_NP=1 (all variants),
+//      DJ_NO_WALK=1 (3), DJ_NO_TAPCACHE=1 (2), dj_set_gather_variants(0) (2 and 3)
+inline int dj_gather_variant(int am, int bm, int pro, const DjIgemmParams& p, bool np23 = true) {
+  static const bool np_off = getenv("DJ_NO_NP") != nullptr, walk_off = getenv("DJ_NO_WALK") != nullptr,
+                    tap_off = getenv("DJ_NO_TAPCACHE") != nullptr;
+  if (np_off || pro == 3) return 0;
+  const bool same_grid = am != 2 || (p.sH == 1 && p.sW == 1 && p.rowH == p.srcH && p.rowW == p.srcW);
+  if (p.KH == 1 && p.KW == 1 && p.pT == 0 && p.pL == 0 && same_grid) return 1;
+  if (!np23 || !g_dj_gather_variants.load(std::memory_order_relaxed)) return 0;
+  if (am == 2) return (!walk_off && p.srcC % bm == 0) ? 3 : 0;
+  return tap_off ? 0 : 2;
+}
+
+// the branch-free kernel's instantiation for a variant (NP 2 exists for forward / input gradient, NP 3 for the weight gradient)
+template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE>
+static int launch_fast_np(int smem_bytes, const DjIgemmParams& p, int splits, hipStream_t s) {
+  const int np = dj_gather_variant(AM, BM, PRO, p);
+  if (np == 1) return launch_fast<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, 1, 1>(smem_bytes, p, splits, s);
+  if constexpr (AM == 2) {
+    if (np == 3) return launch_fast<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, 1, 3>(smem_bytes, p, splits, s);
+  } else {
+    if (np == 2) return launch_fast<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, 1, 2>(smem_bytes, p, splits, s);
+  }
+  return launch_fast<BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, 1, 0>(smem_bytes, p, splits, s);
+}
+
+// fast = 0: generic kernel; 1: branch-free kernel; 2: branch-free kernel with the affine prologue; 3: with the
+// residual-add prologue
 template <int BM, int BN, int WM, int WN, int AM, int BMD, int NSTAGE>
 static int launch_one(const DjIgemmParams& p, int splits, hipStream_t s, int fast) {
   using Cfg = DjIgemmCfg<BM, BN, WM, WN, AM, BMD>;
   static std::atomic<bool> done[1] = {{false}};
   const int smem_fast = Cfg::SMEM_BYTES / 2 * ((NSTAGE == 2 || NSTAGE == 4) ? 2 : 1);
-  {
-    // 1x1 kernels without padding: the variant that does no per-K-step bounds arithmetic (NP, see dj_igemm_fast.h); for
-    // the weight gradient also stride 1 (input pixel == output pixel)
-    static const bool np_off = getenv("DJ_NO_NP") != nullptr;
-    const bool same_grid = (AM != 2) || (p.sH == 1 && p.sW == 1 && p.rowH == p.srcH && p.rowW == p.srcW);
-    if ((fast == 1 || fast == 2) && p.KH == 1 && p.KW == 1 && p.pT == 0 && p.pL == 0 && same_grid && !np_off) {
-      if (fast == 1)
-        return launch_fast<BM, BN, WM, WN, AM, BMD, 0, NSTAGE, 0, 1, 1>(smem_fast, p, splits, s);
-      return launch_fast<BM, BN, WM, WN, AM, BMD, 1, NSTAGE, 0, 1, 1>(smem_fast, p, splits, s);
-    }
-    if constexpr (AM == 2) {
-      // weight gradient with taps / padding / stride whose tiles lie under one tap each: incremental pixel walk (NP 3)
-      static const bool walk_off = getenv("DJ_NO_WALK") != nullptr;
-      if ((fast == 1 || fast == 2) && !np_off && !walk_off && p.srcC % BM == 0) {
-        if (fast == 1)
-          return launch_fast<BM, BN, WM, WN, AM, BMD, 0, NSTAGE, 0, 1, 3>(smem_fast, p, splits, s);
-        return launch_fast<BM, BN, WM, WN, AM, BMD, 1, NSTAGE, 0, 1, 3>(smem_fast, p, splits, s);
-      }
-    }
-    if constexpr (AM != 2) {
-      // kernels with taps / padding: per-tap row offsets cached across the K-steps of a tap (NP 2)
-      static const bool ht_off = getenv("DJ_NO_TAPCACHE") != nullptr;
-      if ((fast == 1 || fast == 2) && !np_off && !ht_off) {
-        if (fast == 1)
-          return launch_fast<BM, BN, WM, WN, AM, BMD, 0, NSTAGE, 0, 1, 2>(smem_fast, p, splits, s);
-        return launch_fast<BM, BN, WM, WN, AM, BMD, 1, NSTAGE, 0, 1, 2>(smem_fast, p, splits, s);
-      }
-    }
-  }
-  if (fast == 1)
-    return launch_fast<BM, BN, WM, WN, AM, BMD, 0, NSTAGE, 0, 1, 0>(smem_fast, p, splits, s);
-  if (fast == 2)
-    return launch_fast<BM, BN, WM, WN, AM, BMD, 1, NSTAGE, 0, 1, 0>(smem_fast, p, splits, s);
-  if (fast == 3) {   // residual-add prologue: forward GEMM only
+  if (fast == 1) return launch_fast_np<BM, BN, WM, WN, AM, BMD, 0, NSTAGE>(smem_fast, p, splits, s);
+  if (fast == 2) return launch_fast_np<BM, BN, WM, WN, AM, BMD, 1, NSTAGE>(smem_fast, p, splits, s);
+  if (fast == 3) {   // forward GEMM only
     if constexpr (AM == 0 && BMD == 0) {
-      return launch_fast<BM, BN, WM, WN, AM, BMD, 3, NSTAGE, 0, 1, 0>(smem_fast, p, splits, s);
+      return launch_fast<BM, BN, WM, WN, AM, BMD, 3, NSTAGE, 1, 0>(smem_fast, p, splits, s);
     } else {
       dj_set_error("residual-add prologue outside the forward GEMM");
       return DJ_ERR_ARG;
@@ -143,22 +149,17 @@ template <int BM, int BN, int AM, int BMD>
 static int launch_k2(const DjIgemmParams& p, int splits, hipStream_t s, int fast) {
   using Cfg = DjIgemmCfg<BM, BN, 2, 2, AM, BMD>;
   if (fast == 1)
-    return launch_fast<BM, BN, 2, 2, AM, BMD, 0, 4, 0, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
+    return launch_fast<BM, BN, 2, 2, AM, BMD, 0, 4, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
   if (fast == 3) {
     if constexpr (AM == 0 && BMD == 0) {
-      return launch_fast<BM, BN, 2, 2, AM, BMD, 3, 4, 0, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
+      return launch_fast<BM, BN, 2, 2, AM, BMD, 3, 4, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
     } else {
       dj_set_error("residual-add prologue outside the forward GEMM");
       return DJ_ERR_ARG;
     }
   }
-  return launch_fast<BM, BN, 2, 2, AM, BMD, 1, 4, 0, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
+  return launch_fast<BM, BN, 2, 2, AM, BMD, 1, 4, 2, 0>(2 * Cfg::SMEM_BYTES, p, splits, s, 512);
 }
-
-extern std::atomic<bool> g_dj_allow_fast;   // dj_conv.hip
-// dj_set_gather_variants (dj_conv.hip): false sends the split-bf16 launches that would take the tap-cache / pixel-walk
-// variants (NP 2 / 3 of dj_igemm_h16.h) to their plain twins
-extern std::atomic<bool> g_dj_gather_variants;
 
 // 0: fp32 results (default; fp32 MFMA or split-bf16 kernel per tuning entry), 5: fp32 MFMA only.  1: forward GEMMs round
 // their operands to fp16, gradient GEMMs (dgrad, wgrad) to bf16 (gradients need the exponent range); 2: bf16 everywhere;

@@ -35,28 +35,14 @@ static int launch_h16_np(int smem_bytes, const DjIgemmParams& p, int splits, hip
 
 template <int BM, int BN, int AM, int BMD, int PRO, int PREC, int BK, int PF, int AT, int BT>
 static int launch_h16_kernel(int smem_bytes, const DjIgemmParams& p, int splits, hipStream_t s) {
-  // 1x1 kernels without padding (for the weight gradient also stride 1, same pixel grid): the variant without per-K-step
-  // bounds arithmetic (NP of dj_igemm_h16.h); DJ_NO_NP=1 switches it off
+  // the gather variant (dj_gather_variant, dj_conv_launch.h); NP 2 / 3 are instantiated for the split-bf16 modes only
   if constexpr (PRO != 3) {
-    static const bool np_off = getenv("DJ_NO_NP") != nullptr;
-    const bool same_grid = (AM != 2) || (p.sH == 1 && p.sW == 1 && p.rowH == p.srcH && p.rowW == p.srcW);
-    if (!np_off && p.KH == 1 && p.KW == 1 && p.pT == 0 && p.pL == 0 && same_grid)
-      return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 1>(smem_bytes, p, splits, s);
-  }
-  // split-bf16 modes, every other geometry (taps, padding, stride, dilation): the weight gradient walks its pixel
-  // incrementally when a tile lies under one filter tap (NP 3), forward and input gradient keep the row offsets of the
-  // current tap (NP 2).  DJ_NO_NP=1 / DJ_NO_WALK=1 / DJ_NO_TAPCACHE=1 and dj_set_gather_variants(0) fall back to NP 0.
-  if constexpr (PRO != 3 && PREC >= 3) {
-    static const bool np_off = getenv("DJ_NO_NP") != nullptr;
-    if (!np_off && g_dj_gather_variants.load(std::memory_order_relaxed)) {
-      if constexpr (AM == 2) {
-        static const bool walk_off = getenv("DJ_NO_WALK") != nullptr;
-        if (!walk_off && p.srcC % BM == 0)
-          return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 3>(smem_bytes, p, splits, s);
-      } else {
-        static const bool ht_off = getenv("DJ_NO_TAPCACHE") != nullptr;
-        if (!ht_off) return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 2>(smem_bytes, p, splits, s);
-      }
+    const int np = dj_gather_variant(AM, BM, PRO, p, PREC >= 3);
+    if (np == 1) return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 1>(smem_bytes, p, splits, s);
+    if constexpr (PREC >= 3 && AM == 2) {
+      if (np == 3) return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 3>(smem_bytes, p, splits, s);
+    } else if constexpr (PREC >= 3) {
+      if (np == 2) return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 2>(smem_bytes, p, splits, s);
     }
   }
   return launch_h16_np<BM, BN, AM, BMD, PRO, PREC, BK, PF, AT, BT, 0>(smem_bytes, p, splits, s);
@@ -112,8 +98,7 @@ static int launch_h16_depth(const DjIgemmParams& p, int splits, hipStream_t s, i
 template <int BM, int BN, int AM, int BMD, int PREC, int AT, int BT>
 static int launch_lowp(const DjIgemmParams& p, int splits, hipStream_t s, int fast, bool deep, bool pf2) {
   // 16-bit tiles in LDS + 16-deep MFMA (dj_igemm_h16.h).  (The round-1 path -- fp32 tiles, fragments rounded at read time,
-  // 8-deep MFMA: PREC != 0 of dj_igemm_fast_kernel -- is no longer instantiated; it was kept for A/B runs until the end
-  // of round 2: 16.63 ms against 15.04 ms per fp16 step when the 16-bit tiles arrived.)
+  // 8-deep MFMA -- is gone.)
   // (round 2: "the 128x128 tile has no registers to spare for a second prefetch set" -- with 16-bit operands a staging set is
   // half the registers, and the tuner decides: 128x128 with two prefetch sets are configurations 4 and 13)
   static const bool pf1 = getenv("DJ_H16_PF1") != nullptr;

@@ -19,6 +19,8 @@
 //   16-byte aligned bases, every operand smaller than 2 GiB.
 #pragma once
 #include "dj_igemm.h"
+#include "dj_gather.h"
+#include "dj_walk.h"
 #include <type_traits>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -28,25 +30,10 @@ __device__ __forceinline__ f32x4 dj_buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned o
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
 }
 
-typedef _Float16 dj_half4 __attribute__((ext_vector_type(4)));
-typedef short dj_short4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ dj_half4 dj_to_half4(f32x4 v) {
-  return dj_half4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};   // round-to-nearest-even
-}
-__device__ __forceinline__ dj_short4 dj_to_bf16x4(f32x4 v) {
-  __bf16 a = (__bf16)v.x, b = (__bf16)v.y, c = (__bf16)v.z, d = (__bf16)v.w;       // v_cvt_pk_bf16_f32 (RNE) on gfx950
-  return dj_short4{__builtin_bit_cast(short, a), __builtin_bit_cast(short, b), __builtin_bit_cast(short, c),
-                   __builtin_bit_cast(short, d)};
-}
-
 // PRO: 0 = plain A, 1 = A*scale[c]+shift[c] (then max(., floor) with floor = 0 or -inf) on in-bounds elements,
 //      3 = residual add: relu(A*scale+shift + A2*scale2+shift2) with a second gathered tensor A2 (1x1 stride-1 forward
 //          only); the workgroups of column tile 0 also store that sum -- the Add()+Activation('relu') output -- to
 //          p.sum_out, so the separate elementwise pass (read, read, write, then read again by this conv) disappears
-// PREC: 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32); 1 = operands rounded to fp16, 2 = to bf16 when the fragments
-//       are read, one v_mfma_f32_32x32x8_{f16,bf16} per 8-deep k group (same lane <-> k mapping as the four fp32
-//       MFMAs it replaces), fp32 accumulation.  HBM and LDS contents stay fp32 ("fp32 master" tensors).
 // KS: 1, or 2 = two 256-thread groups per workgroup, each with its own LDS ring, take alternate K-steps of the SAME
 //       output tile and add their accumulators through LDS before the epilogue: twice the waves per SIMD for launches
 //       that have too few tiles to fill the CUs (19x19 and 10x10 maps at batch 32), no atomics, BN statistics intact.
@@ -63,7 +50,7 @@ __device__ __forceinline__ dj_short4 dj_to_bf16x4(f32x4 v) {
 //       channel position to it and nothing else.
 //   3 = weight gradient with taps / padding / stride (A-mode 2) when in_c is a multiple of BM: the tile's BM rows lie
 //       under ONE filter tap, and a thread's pixel moves by the same number of pixels every K-step.  The pixel is
-//       decomposed once; afterwards (ow, oh) and the byte offset of the tapped input pixel advance by wave-uniform
+//       decomposed once (dj_walk.h); afterwards (ow, oh) and the byte offset of the tapped input pixel advance by wave-uniform
 //       constants with two carries (row end, image end) -- ~15 vector instructions per K-step where the float-reciprocal
 //       decomposition, the per-chunk tap arithmetic and its three integer multiplies took ~75 (64x64 tile: 134 -> ~75
 //       per 16 MFMAs, and the multiplies are quarter rate).
@@ -72,8 +59,7 @@ __device__ __forceinline__ dj_short4 dj_to_bf16x4(f32x4 v) {
 //      launches that do not ask for it keep their occupancy.
 //      2 = the masked accumulate (DjIgemmParams::mask_x; input-gradient GEMM only): the store loops are replaced by twins that
 //      also load the ReLU mask (dj_store_full_tile_relumask) -- again an instantiation of its own, the others are untouched.
-template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE = 2, int PREC = 0, int KS = 1, int NP = 0,
-          int EPI = 0>
+template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE = 2, int KS = 1, int NP = 0, int EPI = 0>
 __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmParams p) {
   static_assert(EPI == 0 || (AM == 1 && BMD == 1), "BatchNormalization backward statistics: input-gradient GEMM only");
   static_assert(EPI != 2 || PRO == 0, "masked accumulate: the input-gradient GEMM has no prologue");
@@ -141,7 +127,7 @@ __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmPa
   if (AM != 2) {
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
-      int m = m0 + ar0 + 32 * j;
+      const int m = m0 + ar0 + 32 * j;
       row_valid |= (m < p.M) ? (1u << j) : 0u;
       if (m < p.M) {
         int img, h, w;
@@ -168,47 +154,35 @@ __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmPa
   } else {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      int mm = m0 + 4 * (ac + 8 * i);
-      a2_ok[i] = mm < p.M;
-      int tap = mm / p.srcC;
-      a2_c[i] = mm - tap * p.srcC;
-      int kh = tap / p.KW;
-      int kw = tap - kh * p.KW;
-      a2_dh[i] = kh * p.dH - p.pT;
-      a2_dw[i] = kw * p.dW - p.pL;
+      const DjGatherChunk g = dj_gather_chunk(p, m0 + 4 * (ac + 8 * i));
+      a2_ok[i] = g.ok;
+      a2_c[i] = g.c;
+      a2_dh[i] = g.dh;
+      a2_dw[i] = g.dw;
       if (PRO) {
         a2_sc[i] = dj_buf_ld4(rS, a2_ok[i] ? (unsigned)a2_c[i] * 4u : DJ_OOB);
         a2_sh[i] = dj_buf_ld4(rT, a2_ok[i] ? (unsigned)a2_c[i] * 4u : DJ_OOB);
       }
       row_valid |= a2_ok[i] ? (1u << i) : 0u;
-      if (NP == 1) a2_c[i] = a2_ok[i] ? a2_c[i] * 4 : (int)0x80000000;    // byte offset of the chunk inside its pixel
+      if (NP == 1) a2_c[i] = a2_ok[i] ? a2_c[i] * 4 : (int)0x80000000;   // byte offset of the chunk inside its pixel
     }
   }
   // NP, A-mode 2: byte offset of this thread's pixel row (pixel kbeg + ar0 of the first K-step), advanced per K-step
   int np_row = (NP == 1 && AM == 2) ? (kbeg + ar0) * p.ldsrc * 4 : 0;
   const int np_step = DJ_BK * p.ldsrc * 4;
-  // NP 3: this thread's output pixel (walk_ow, walk_oh), its index walk_kp, and the byte offset walk_off of chunk 0 at
-  // the tapped input pixel; walk_c0/1/2: what a K-step, a row carry and an image carry add to that offset
-  int walk_ow = 0, walk_oh = 0, walk_kp = 0, walk_off = 0;
-  int walk_sw = 0, walk_sh = 0, walk_c0 = 0, walk_c1 = 0, walk_c2 = 0, walk_dh = 0, walk_dw = 0;
+  // NP 3: this thread's output pixel, its index and the byte offset of chunk 0 at the tapped input pixel (dj_walk.h, as
+  // in dj_igemm_h16.h); the tile lies under the tap (walk_dh, walk_dw)
+  const DjWalkGeom walk_g{p.rowH, p.rowW, p.srcH, p.srcW, p.sH, p.sW, p.ldsrc * 4};
+  DjWalkStep walk_s{};
+  DjWalkPos walk{};
+  int walk_dh = 0, walk_dw = 0;
   if (NP == 3) {
     const int tap = m0 / p.srcC, cb = m0 - tap * p.srcC;
     const int kh = tap / p.KW, kw = tap - kh * p.KW;
     walk_dh = kh * p.dH - p.pT;
     walk_dw = kw * p.dW - p.pL;
-    const int hw = p.rowH * p.rowW;
-    const int s_img = KSTEP / hw, r = KSTEP - s_img * hw;
-    walk_sh = r / p.rowW;
-    walk_sw = r - walk_sh * p.rowW;
-    const int pix4 = p.ldsrc * 4;
-    walk_c0 = ((s_img * p.srcH + walk_sh * p.sH) * p.srcW + walk_sw * p.sW) * pix4;
-    walk_c1 = (p.sH * p.srcW - p.rowW * p.sW) * pix4;
-    walk_c2 = (p.srcH - p.rowH * p.sH) * p.srcW * pix4;
-    walk_kp = kbeg + ar0;
-    const int img = walk_kp / hw, rem = walk_kp - img * hw;
-    walk_oh = rem / p.rowW;
-    walk_ow = rem - walk_oh * p.rowW;
-    walk_off = ((img * p.srcH + walk_oh * p.sH + walk_dh) * p.srcW + walk_ow * p.sW + walk_dw) * pix4 + (cb + 4 * ac) * 4;
+    walk_s = dj_walk_step(walk_g, KSTEP);
+    walk = dj_walk_init(walk_g, kbeg + ar0, walk_dh, walk_dw, (cb + 4 * ac) * 4);
   }
   int b_off[NB];
   bool b_ok[NB];
@@ -324,37 +298,19 @@ __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmPa
       np_row += np_step;
     } else if (NP == 3) {
       // 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate): coordinates and strides are far below 2^23
-      const int ih = __mul24(walk_oh, p.sH) + walk_dh, iw = __mul24(walk_ow, p.sW) + walk_dw;
-      const bool ok = live & (walk_kp < kend) & ((unsigned)ih < (unsigned)p.srcH) & ((unsigned)iw < (unsigned)p.srcW);
-      const unsigned voff = ok ? (unsigned)walk_off : 0x80000000u;   // stays out of range with the chunk offsets added
+      const int ih = __mul24(walk.oh, p.sH) + walk_dh, iw = __mul24(walk.ow, p.sW) + walk_dw;
+      const bool ok = live & dj_walk_inside(walk_g, walk, ih, iw, kend);
+      const unsigned voff = ok ? (unsigned)walk.off : 0x80000000u;   // stays out of range with the chunk offsets added
       a_valid = ok ? 0xFFFFFFFFu : 0u;
 #pragma unroll
-      for (int i = 0; i < NA; ++i) ra[i] = dj_buf_ld4(rA, voff + 128u * i);
-      // on to the pixel KSTEP further: s_w < W and s_h < H, so each carry is at most one
-      walk_kp += KSTEP;
-      walk_ow += walk_sw;
-      const bool c1 = walk_ow >= p.rowW;
-      walk_ow -= c1 ? p.rowW : 0;
-      walk_oh += walk_sh + (c1 ? 1 : 0);
-      const bool c2 = walk_oh >= p.rowH;
-      walk_oh -= c2 ? p.rowH : 0;
-      walk_off += walk_c0 + (c1 ? walk_c1 : 0) + (c2 ? walk_c2 : 0);
+      for (int i = 0; i < NA; ++i) ra[i] = dj_buf_ld4(rA, voff + 128u * i);   // a thread's chunks: 4 * 8 channels apart
+      dj_walk_advance(walk_g, walk_s, walk);
     } else {
       a_valid = 0;
       const int kp = kcur + ar0;
-      const int hw = p.rowH * p.rowW;
-      int img = (int)((float)kp * p.inv_rowHW);
-      int rem = kp - img * hw;
-      int adj = (rem < 0) ? -1 : ((rem >= hw) ? 1 : 0);  // float reciprocal is within one of the quotient
-      img += adj;
-      rem -= adj * hw;
-      int oh = (int)((float)rem * p.inv_rowW);
-      int ow = rem - oh * p.rowW;
-      int adj2 = (ow < 0) ? -1 : ((ow >= p.rowW) ? 1 : 0);
-      oh += adj2;
-      ow -= adj2 * p.rowW;
+      const DjPixel px = dj_pixel_decompose(p, kp);
       const bool rowok = live && kp < kend;
-      const int h0 = oh * p.sH, w0 = ow * p.sW, pb = img * p.srcH * p.srcW;
+      const int h0 = px.oh * p.sH, w0 = px.ow * p.sW, pb = px.img * p.srcH * p.srcW;
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         int h = h0 + a2_dh[i], w = w0 + a2_dw[i];
@@ -489,28 +445,7 @@ __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmPa
     }
   };
   auto mma = [&](const Frag& f) {
-    if (PREC == 1) {
-      dj_half4 ah[TM], bh[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ah[i] = dj_to_half4(f.a[i]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bh[j] = dj_to_half4(f.b[j]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x8f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-    } else if (PREC == 2) {
-      dj_short4 ah[TM], bh[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) ah[i] = dj_to_bf16x4(f.a[i]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bh[j] = dj_to_bf16x4(f.b[j]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(ah[i], bh[j], acc[i][j], 0, 0, 0);
-    } else if (DUAL) {
+    if (DUAL) {
 #pragma unroll
       for (int e = 0; e < 4; e += 2) {
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[0][e], f.b[0][e], acc[0][0], 0, 0, 0);

@@ -4,9 +4,9 @@
 // rounded to fp16 (forward) or bf16 (gradients) ONCE, when a thread stores its piece of the tile to LDS, and fed to
 // v_mfma_f32_32x32x16_{f16,bf16} -- the 16-deep CDNA4 instruction, fp32 accumulation.  HBM tensors stay fp32.
 //
-// What changed against the PREC != 0 path of dj_igemm_fast.h (fp32 tiles in LDS, every wave converting the fragments it
-// reads, 8-deep MFMA): half the LDS bytes, each element converted once instead of once per reading wave, and half the
-// MFMA instructions per K-step.
+// What changed against the first reduced-precision path (since removed: fp32 tiles in LDS, every wave converting the
+// fragments it reads, 8-deep MFMA): half the LDS bytes, each element converted once instead of once per reading wave,
+// and half the MFMA instructions per K-step.
 //
 // LDS images (16-bit elements), one K-step = BK k (32, or 64 for forward / input gradient: see BK below):
 //   * k-contiguous operand (A of forward / input gradient, B of the input gradient): [rows][BK k], pitch BK + 8 elements
@@ -52,7 +52,6 @@
 #pragma once
 #include "dj_igemm.h"
 #include "dj_igemm_fast.h"
-#include "dj_walk.h"
 
 typedef short dj_tr4 __attribute__((__vector_size__(4 * sizeof(short))));   // what the transposing read returns
 typedef short dj_s16x8 __attribute__((ext_vector_type(8)));
@@ -60,6 +59,17 @@ typedef _Float16 dj_half8 __attribute__((ext_vector_type(8)));
 typedef __bf16 dj_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short __attribute__((address_space(3))) dj_lds_short;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 dj_half4 __attribute__((ext_vector_type(4)));
+typedef short dj_short4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ dj_half4 dj_to_half4(f32x4 v) {
+  return dj_half4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};   // round-to-nearest-even
+}
+__device__ __forceinline__ dj_short4 dj_to_bf16x4(f32x4 v) {
+  __bf16 a = (__bf16)v.x, b = (__bf16)v.y, c = (__bf16)v.z, d = (__bf16)v.w;       // v_cvt_pk_bf16_f32 (RNE) on gfx950
+  return dj_short4{__builtin_bit_cast(short, a), __builtin_bit_cast(short, b), __builtin_bit_cast(short, c),
+                   __builtin_bit_cast(short, d)};
+}
 
 // A thread's 4-element piece of an operand between its buffer load and its LDS store, as the operand is stored in HBM
 template <int DT>
@@ -249,7 +259,7 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
   } else if (AM != 2) {
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
-      int m = m0 + ar0 + ARPP * j;
+      const int m = m0 + ar0 + ARPP * j;
       if (m < p.M) {
         int img, h, w;
         dj_row_decompose(p, m, img, h, w);
@@ -268,14 +278,11 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
   } else {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
-      int mm = m0 + 4 * (ac + ACG * i);
-      a2_ok[i] = mm < p.M;
-      int tap = mm / p.srcC;
-      a2_c[i] = mm - tap * p.srcC;
-      int kh = tap / p.KW;
-      int kw = tap - kh * p.KW;
-      a2_dh[i] = kh * p.dH - p.pT;
-      a2_dw[i] = kw * p.dW - p.pL;
+      const DjGatherChunk g = dj_gather_chunk(p, m0 + 4 * (ac + ACG * i));
+      a2_ok[i] = g.ok;
+      a2_c[i] = g.c;
+      a2_dh[i] = g.dh;
+      a2_dw[i] = g.dw;
       if (PRO) {
         a2_sc[i] = dj_buf_ld4(rS, a2_ok[i] ? (unsigned)a2_c[i] * 4u : DJ_OOB);
         a2_sh[i] = dj_buf_ld4(rT, a2_ok[i] ? (unsigned)a2_c[i] * 4u : DJ_OOB);
@@ -441,19 +448,9 @@ __global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p
     } else {
       a_valid = 0;
       const int kp = kcur + ar0;
-      const int hw = p.rowH * p.rowW;
-      int img = (int)((float)kp * p.inv_rowHW);
-      int rem = kp - img * hw;
-      int adj = (rem < 0) ? -1 : ((rem >= hw) ? 1 : 0);
-      img += adj;
-      rem -= adj * hw;
-      int oh = (int)((float)rem * p.inv_rowW);
-      int ow = rem - oh * p.rowW;
-      int adj2 = (ow < 0) ? -1 : ((ow >= p.rowW) ? 1 : 0);
-      oh += adj2;
-      ow -= adj2 * p.rowW;
+      const DjPixel px = dj_pixel_decompose(p, kp);
       const bool rowok = live && kp < kend;
-      const int h0 = oh * p.sH, w0 = ow * p.sW, pb = img * p.srcH * p.srcW;
+      const int h0 = px.oh * p.sH, w0 = px.ow * p.sW, pb = px.img * p.srcH * p.srcW;
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         int h = h0 + a2_dh[i], w = w0 + a2_dw[i];

@@ -1,4 +1,4 @@
-// Incremental pixel walk of the weight gradient's gathered operand (NP 3 of dj_igemm_h16.h).
+// Incremental pixel walk of the weight gradient's gathered operand (NP 3 of dj_igemm_fast.h and of dj_igemm_h16.h).
 //
 // The weight-gradient GEMM reduces over output pixels: K-step t of a thread reads output pixel kp = kp0 + t * step
 // (pixels are numbered image-major, then row, then column, over the rowH x rowW output map) and, under ONE filter tap
@@ -11,8 +11,8 @@
 //   oh += sh + c1;       carry c2 when oh reaches rowH (at most once: oh + sh + 1 <= 2 rowH - 1)
 //   off += c0 + (c1 ? add1 : 0) + (c2 ? add2 : 0)
 //
-// Plain C++: the kernels include it, and so does the host program that checks the walk against the direct
-// decomposition for every K-step of a grid of geometries (tests/pixel_walk_check.cpp).
+// Plain C++: both kernel families include it, and so does the host program that checks the walk against the direct
+// decomposition for every K-step of a grid of geometries (tests/pixel_walk_check.cpp) -- the check covers both.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)

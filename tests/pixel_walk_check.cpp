@@ -1,5 +1,7 @@
 // Host check of the weight gradient's incremental pixel walk (csrc/dj_walk.h) against the direct decomposition of the
-// pixel index that the plain kernels redo every K-step.  Built and run by tests/test_pixel_walk_cpu.py with
+// pixel index that the plain kernels redo every K-step.  Both kernel families walk with this header: the split-bf16
+// kernels in K-steps of 16 / 32, the fp32 MFMA kernels in K-steps of 32.  What is walked here: 4-byte elements, K-steps
+// of 16 and 32, a thread's chunks 4 * 256 / step channels apart.  Built and run by tests/test_pixel_walk_cpu.py with
 // -fsanitize=address,undefined; prints one summary line and exits non-zero on the first mismatch.
 #include <cstdio>
 #include <cstdlib>

@@ -1,7 +1,9 @@
-"""Split-bf16 modes (float32x3 / float32x6): the gather variants of dj_igemm_h16.h -- per-tap row offsets cached across the
-K-steps of a tap (NP 2: forward, input gradient) and the incremental pixel walk (NP 3: weight gradient) -- against their
-plain twins (NP 0), which redo the bounds and address arithmetic every K-step.  A twin pair sums the same products in
-the same order, so every comparison is torch.equal; `dj_set_gather_variants` picks the twin inside one process.
+"""Both branch-free kernel families -- the split-bf16 kernels of dj_igemm_h16.h (float32x3 / float32x6) and the fp32 MFMA
+kernels of dj_igemm_fast.h (float32_mfma: compute mode 5, configuration indices [0, N)) --: their gather variants --
+per-tap row offsets cached across the K-steps of a tap (NP 2: forward, input gradient) and the incremental pixel walk
+(NP 3: weight gradient, dj_walk.h) -- against their plain twins (NP 0), which redo the bounds and address arithmetic
+every K-step.  A twin pair sums the same products in the same order, so every comparison is torch.equal;
+`dj_set_gather_variants` picks the twin of either family inside one process.
 
 Geometries: the smallest at which each carry and edge of the walk / each tap edge occurs (see GEOMS).  The prologue's
 shift is larger in magnitude than the data, so a padding pixel that is not zeroed AFTER the prologue shows.
@@ -9,7 +11,9 @@ shift is larger in magnitude than the data, so a padding pixel that is not zeroe
 Split-K in the bit-equality test: the forward pass goes through slabs + the fixed-order reduction; the gradients have
 atomics only, and are compared at TWO K ranges -- two commutative additions onto a zeroed tensor, the same bits in either
 arrival order -- which is what makes a K range that starts in the middle of the reduction comparable at all.  The
-fp64-oracle test runs the weight gradient at three K ranges (atomics) at the bounds of tests/test_x3_gpu.py."""
+fp64-oracle test runs the weight gradient at three K ranges (atomics) at the bounds of tests/test_x3_gpu.py;
+float32_mfma takes the float32x6 bound: against the fp64 oracle the fp32 MFMA kernels and the float32x6 kernels lie
+equally far from it (include/dj_hip.h, dj_set_compute_mode)."""
 import functools
 
 import pytest
@@ -18,7 +22,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 TOL = {"float32x3": 3e-5, "float32x6": 2e-6}   # rel-L2 per GEMM: the bounds of tests/test_x3_gpu.py
-MODES = ["float32x6", "float32x3"]
+TOL["float32_mfma"] = TOL["float32x6"]
+MODES = ["float32x6", "float32x3", "float32_mfma"]
 
 # (batch, H, W, Cin, Cout, k, stride, padding, dilation)
 GEOMS = [

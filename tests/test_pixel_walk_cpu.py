@@ -1,7 +1,8 @@
-"""CPU: the incremental pixel walk of the split-bf16 weight gradient (csrc/dj_walk.h, NP 3 of dj_igemm_h16.h) gives,
-for every thread row and every K-step of every K chunk, exactly the (in-bounds flag, byte offset) of the direct pixel
-decomposition.  tests/pixel_walk_check.cpp walks the grid (maps 1x1 .. 19x19, strides 1 / 2, dilation 1 / 6, 'same' and
-'valid' padding, K-steps of 16 and 32, chunks that end mid-row and mid-image, batch 1 .. 3); it is built here as a
+"""CPU: the incremental pixel walk of the weight gradient (csrc/dj_walk.h: NP 3 of both kernel families, the fp32 MFMA
+kernels of dj_igemm_fast.h and the split-bf16 kernels of dj_igemm_h16.h) gives, for every thread row and every K-step of
+every K chunk, exactly the (in-bounds flag, byte offset) of the direct pixel decomposition.  tests/pixel_walk_check.cpp
+walks the grid (maps 1x1 .. 19x19, strides 1 / 2, dilation 1 / 6, 'same' and 'valid' padding, K-steps of 16 and 32 -- 32
+is also the fp32 kernels' step --, chunks that end mid-row and mid-image, batch 1 .. 3); it is built here as a
 stand-alone program with the address and undefined-behaviour sanitizers and run directly."""
 import os
 import re

@@ -1,0 +1,14 @@
+"""Training configuration for `vgga_dct`, the VGG-A classifier on JPEG-DCT inputs: the settings of
+classification_part/config/vggA_dct/config_file.py (batch 256, 5000 steps x 120 epochs, Nesterov SGD at lr 0.01,
+top-1 / top-5) on the TrainingConfiguration surface of config/resnet/config_file.py.  Everything but the builder and the
+project name is shared with config/vggD_dct, in jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.vgg_dct_configuration, whose
+docstring states the `DJ_*` data rules.
+
+    python3 training.py -c config/vggA_dct --archi vggA_dct --horovod False --use_pretrained_weights False"""
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks import vgga_dct
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.vgg_dct_configuration import VGGDCTTrainingConfiguration
+
+
+class TrainingConfiguration(VGGDCTTrainingConfiguration):
+    def __init__(self):
+        super(TrainingConfiguration, self).__init__(vgga_dct, "vgg-dct")

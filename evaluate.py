@@ -17,7 +17,8 @@ from os.path import isfile, join
 parser = argparse.ArgumentParser()
 parser.add_argument("experiment", help="Experiment directory written by training.py.")
 parser.add_argument("weights", help="Weights file to evaluate, usually one of the experiment's checkpoints.")
-parser.add_argument("--archi", default="late_concat_rfa_thinner", help="Network architecture, as given to training.py.")
+parser.add_argument("--archi", default="late_concat_rfa_thinner", help="Network architecture, as given to training.py "
+                    "(the ResNet50-DCT names, resnet_rgb, vggA_dct or vggD_dct).")
 args = parser.parse_args()
 
 DCT_ARCHIS = ["cb5_only", "deconv", "up_sampling", "up_sampling_rfa", "y_cb4_cbcr_cb5", "late_concat_rfa_thinner",

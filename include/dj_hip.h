@@ -679,6 +679,24 @@ int dj_eval_rank(const int* rec_class, const int* rec_image, const float* rec_co
 int dj_eval_accumulate(const float* y_true, const float* probs, long rows, int C, const int* ks_host, int n_k,
                        const float* loss_mean, double loss_weight, double* acc, long long* counts, void* stream);
 
+/* ---- Dropout (keras.layers.Dropout in training plans; C/vgg_jpeg_keras/networks/networks_dct.py, the two layers between
+ * fc1, fc2 and predictions).  keras/dropout.py states it in numpy; both entry points equal that statement bit for bit.
+ * No state and no stored mask: element i of a contiguous float32 tensor of n elements is kept iff lane (i & 3) of
+ * Philox4x32-10(counter = (lo32(i >> 2), hi32(i >> 2), ctr2, ctr3), key = (key0, key1)) is >= threshold, so the mask of an
+ * element does not depend on n and the backward pass regenerates the forward's mask from the same six words.  The layer
+ * packs key0 = its seed, key1 = the data-parallel rank, (ctr2, ctr3) = the low and high half of the optimizer's step
+ * count; threshold = min(int(rate * 2^32), 2^32 - 1) and scale = (float)(1 / (1 - rate)) are computed on the host.
+ * dj_dropout_fwd: y[i] = (x[i] * scale) * keep_i with keep_i 0.0f / 1.0f -- a product, so an Inf or NaN at a dropped
+ * position gives NaN; y == x is allowed.  dj_dropout_bwd: dx[i] = (dy[i] * scale) * keep_i, added to dx[i] when beta == 1.
+ * One thread per four consecutive elements in a grid-stride loop of at most dj_dropout_groups_per_pass() threads; 16-byte
+ * loads and stores when both pointers are 16-byte aligned, element by element otherwise and in the n % 4 tail.  Refused
+ * before any launch: a NULL pointer, n <= 0, beta outside {0, 1}. ---- */
+long dj_dropout_groups_per_pass(void);
+int dj_dropout_fwd(const float* x, float* y, long n, unsigned threshold, float scale, unsigned key0, unsigned key1,
+                   unsigned ctr2, unsigned ctr3, void* stream);
+int dj_dropout_bwd(const float* dy, float* dx, long n, unsigned threshold, float scale, unsigned key0, unsigned key1,
+                   unsigned ctr2, unsigned ctr3, int beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ There is no CPU fallback: if the library is missing the import of any compute en
 raises, and every call checks the return code and raises `DjError` with dj_last_error()."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DJ_LIB_PATH") or os.path.join(_HERE, "csrc", "libdj_hip.so")   # override: kernel experiments
@@ -200,6 +200,9 @@ SIGNATURES = {
     "dj_eval_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "dj_eval_accumulate": (c_int, [FP, FP, c_long, c_int, c_void_p, c_int, FP, c_double, c_void_p, c_void_p, c_void_p]),
+    "dj_dropout_groups_per_pass": (c_long, []),
+    "dj_dropout_fwd": (c_int, [FP, FP, c_long, c_uint32, c_float, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p]),
+    "dj_dropout_bwd": (c_int, [FP, FP, c_long, c_uint32, c_float, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_void_p]),
 }
 
 

@@ -1,6 +1,6 @@
-"""Keras-2.2.4-style layers, limited to what the reference's ResNet50-DCT / SSD300 builders use
+"""Keras-2.2.4-style layers, limited to what the reference's ResNet50-DCT / SSD300 / VGG-DCT builders use
 (localisation_part/models/keras_ssd300_dct_j2d_resnet.py:22-36,
-classification_part/vgg_jpeg_keras/networks/resnet_dct.py), each with a `lower()` that turns it into
+classification_part/vgg_jpeg_keras/networks/resnet_dct.py, .../networks_dct.py), each with a `lower()` that turns it into
 C-ABI launches inside an engine.Plan.  Same constructor keywords, defaults, auto-naming and
 `_keras_shape` / `output_shape` attributes as Keras, so builder code reads like the reference's."""
 import os
@@ -14,6 +14,7 @@ from ..engine import GradRef, Value, call, launcher, query, rows_of
 from .. import kernels as Kn
 from . import backend as K
 from . import initializers
+from .dropout import dropout_scale, dropout_threshold, dropout_words
 
 _SERIAL = [0]
 
@@ -1246,6 +1247,75 @@ class GlobalAveragePooling2D(Layer):
             dy = out.grad.buf
             dx, beta = plan.grad_of(x)
             plan.emit_bwd(lambda: call("dj_global_avg_pool_bwd", dy, dx, b, h * w, c, beta))
+
+        plan.on_backward(build_backward)
+        return out
+
+
+class Dropout(Layer):
+    """keras.layers.Dropout(rate, noise_shape=None, seed=None) -- between fc1, fc2 and predictions of the VGG-DCT
+    classifiers (classification_part/vgg_jpeg_keras/networks/networks_dct.py).  No weights and no stored mask: keras/dropout.py
+    states the mask as a function of (layer seed, data-parallel rank, optimizer step, element index); a training plan
+    makes one dj_dropout_fwd launch and one dj_dropout_bwd launch that regenerates the mask, every other plan and
+    rate == 0 make the layer an alias of its input.  `seed=None` draws the layer's seed, at construction, from the
+    generator K.set_random_seed seeds.  The layer's input and output are fp32 tensors under every K.set_floatx mode: it
+    sits between Dense outputs of `batch` rows, which the lowering never stores in 16 bits, and it refuses a 16-bit
+    input."""
+
+    def __init__(self, rate, noise_shape=None, seed=None, **kwargs):
+        super(Dropout, self).__init__(**kwargs)
+        rate = float(rate)
+        if not 0.0 <= rate < 1.0:
+            raise ValueError("Dropout rate must lie in [0, 1), got %r" % (rate,))
+        if noise_shape is not None:
+            raise NotImplementedError("Dropout noise_shape (the reference's networks never pass one)")
+        self.rate = rate
+        self.noise_shape = None
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 32, (1,), generator=K.generator(), dtype=torch.int64))
+        self.seed = int(seed) & 0xFFFFFFFF
+
+    def get_config(self):
+        cfg = super(Dropout, self).get_config()
+        cfg.update(rate=self.rate, noise_shape=None, seed=self.seed)
+        return cfg
+
+    def lower(self, plan, model, ins):
+        x = ins[0]
+        if not plan.training or self.rate == 0.0:
+            return x
+        xbuf = _materialised(x, self.name, plan)
+        if xbuf.dtype != torch.float32:
+            raise NotImplementedError("%s: Dropout works on fp32 tensors only, its input is %s" % (self.name, xbuf.dtype))
+        assert xbuf.is_contiguous()
+        n = xbuf.numel()
+        y = plan.empty(*xbuf.shape)
+        threshold, scale = dropout_threshold(self.rate), float(dropout_scale(self.rate))
+        seed = self.seed
+        drawn = {}     # the words of the forward launch of this step: the backward launch regenerates the same mask
+
+        def forward():
+            rank = model.dist.rank if model.dist is not None else 0
+            drawn["words"] = dropout_words(seed, rank, model.optimizer.iterations if model.optimizer is not None else 0)
+            call("dj_dropout_fwd", xbuf, y, n, threshold, scale, *drawn["words"])
+        forward.dj_entry = ("dj_dropout_fwd", self.name)      # structure checks find the launch by it
+        plan.emit(forward)
+        out = Value(y, needs_grad=x.needs_grad, name=self.name)
+        out.dropout = self
+
+        def build_backward():
+            if out.grad is None or not x.needs_grad:
+                return
+            assert out.grad.mask_y is None
+            dy = out.grad.buf
+            assert dy.is_contiguous() and dy.dtype == torch.float32
+            dx, beta = plan.grad_of(x)
+            assert dx.is_contiguous() and dx.dtype == torch.float32
+
+            def backward():
+                call("dj_dropout_bwd", dy, dx, n, threshold, scale, *(drawn["words"] + (int(beta),)))
+            backward.dj_entry = ("dj_dropout_bwd", self.name)
+            plan.emit_bwd(backward)
 
         plan.on_backward(build_backward)
         return out

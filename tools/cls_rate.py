@@ -1,15 +1,36 @@
-"""Training images/s of the classifier workloads (BASELINE configs 1-2): ResNet50Custom(deconv) B=64, ResNet50RGB B=64."""
+"""Training images/s of the classifier workloads at B=64.  Without arguments: BASELINE configs 1-2 (ResNet50Custom(deconv),
+late_concat_rfa_thinner, ResNet50RGB).  Names on the command line select among those and the VGG-DCT classifiers:
+
+    DJ_AUTOTUNE=1 python tools/cls_rate.py vgga_dct vggd_dct --runs 3 --steps 200
+
+--runs N times N blocks of --steps steps (default 20) per model and prints every block and their median."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from jpeg_detection_resnet_ssd_amd.keras import backend as K
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks import vgga_dct, vggd_dct
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 from jpeg_detection_resnet_ssd_amd.data import synthetic_dct as sd
+MODELS = {
+    "deconv": ("deconv classifier (Y 28x28x64, Cb/Cr 14x14x64)", lambda: ResNet50Custom(weights=None, archi="deconv"), 64),
+    "late_concat_rfa_thinner": ("late_concat_rfa_thinner classifier", lambda: ResNet50Custom(weights=None, archi="late_concat_rfa_thinner"), 64),
+    "resnet_rgb": ("resnet_rgb classifier (224x224x3)", lambda: ResNet50RGB(weights=None), 64),
+    "vgga_dct": ("vgga_dct classifier (Y 28x28x64, CbCr 14x14x128)", lambda: vgga_dct(1000), 64),
+    "vggd_dct": ("vggd_dct classifier (Y 28x28x64, CbCr 14x14x128)", lambda: vggd_dct(1000), 64),
+}
+argv, opts = sys.argv[1:], {"--runs": 1, "--steps": 20}
+for flag in opts:
+    if flag in argv:
+        i = argv.index(flag)
+        opts[flag] = int(argv[i + 1])
+        del argv[i:i + 2]
+runs, n = opts["--runs"], opts["--steps"]
+unknown = [a for a in argv if a not in MODELS]
+if unknown:
+    sys.exit("unknown model %s: choose among %s" % (unknown, ", ".join(MODELS)))
 rng = np.random.default_rng(0)
-for name, build, B in (("deconv classifier (Y 28x28x64, Cb/Cr 14x14x64)", lambda: ResNet50Custom(weights=None, archi="deconv"), 64),
-                       ("late_concat_rfa_thinner classifier", lambda: ResNet50Custom(weights=None, archi="late_concat_rfa_thinner"), 64),
-                       ("resnet_rgb classifier (224x224x3)", lambda: ResNet50RGB(weights=None), 64)):
+for name, build, B in [MODELS[a] for a in (argv or ["deconv", "late_concat_rfa_thinner", "resnet_rgb"])]:
     K.clear_session()
     m = build()
     m.compile(optimizer=SGD(lr=0.1, momentum=0.9, decay=1e-4, nesterov=True), loss="categorical_crossentropy")
@@ -19,10 +40,14 @@ for name, build, B in (("deconv classifier (Y 28x28x64, Cb/Cr 14x14x64)", lambda
     plan = m._plan(B, True, True)
     m._upload(plan, x if len(x) > 1 else x[0], y)
     for _ in range(3): m.run_train_step(plan)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    n = 20
-    for _ in range(n): m.run_train_step(plan)
-    torch.cuda.synchronize()
-    print("%-52s B=%d: %.0f img/s" % (name, B, B * n / (time.perf_counter() - t0)), flush=True)
+    rates = []
+    for _ in range(runs):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(n): m.run_train_step(plan)
+        torch.cuda.synchronize()
+        rates.append(B * n / (time.perf_counter() - t0))
+        print("%-52s B=%d: %.0f img/s" % (name, B, rates[-1]), flush=True)
+    if runs > 1:
+        print("%-52s B=%d: median of %d: %.0f img/s" % (name, B, runs, float(np.median(rates))), flush=True)
     del m, plan
     torch.cuda.empty_cache()

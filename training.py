@@ -28,7 +28,8 @@ parser.add_argument("-c", "--configuration", help="Path to the directory contain
 parser.add_argument("--horovod")
 parser.add_argument("--use_pretrained_weights", help="Whether to load pretrained weights from Keras for ResnetRGB")
 parser.add_argument("--archi", default="late_concat_rfa_thinner", help="""The network architecture to use, value can be :\n
-* cb5_only, deconv, up_sampling, up_sampling_rfa, y_cb4_cbcr_cb5, late_concat_rfa_thinner, late_concat_more_channels, resnet_rgb""")
+* cb5_only, deconv, up_sampling, up_sampling_rfa, y_cb4_cbcr_cb5, late_concat_rfa_thinner, late_concat_more_channels, resnet_rgb (with -c config/resnet or config/resnetRGB)
+* vggA_dct, vggD_dct (with -c config/vggA_dct or config/vggD_dct, whose configuration takes no arguments)""")
 parser.add_argument("--epochs", type=int, default=None)
 parser.add_argument("--steps_per_epoch", type=int, default=None)
 parser.add_argument("--batch_size", type=int, default=None)

@@ -36,16 +36,22 @@ extern "C" {
 const char* dj_last_error(void);
 /* Version of this interface: bumped whenever an entry point is added or the meaning of an argument changes
  * (2: the `beta` / `relu` bit fields, the workspace and BatchNormalization-backward-statistics entry points, the per-thread
- * arithmetic mode; 3: the dtype-carrying `_t` entry points for 16-bit tensors in HBM, the tuner direction 9).  A binding
+ * arithmetic mode; 3: storage-type codes for 16-bit tensors in HBM, the tuner direction 9; 4: one entry point per
+ * convolution GEMM, taking an argument struct; their `_ws` / `_addrelu` / `_bn` / `_bnbwd` / `_relumask` / `_t` forms are gone).  A binding
  * written for one version must refuse a library that reports another (jpeg_detection_resnet_ssd_amd/_lib.py does). */
-#define DJ_ABI_VERSION 3
+#define DJ_ABI_VERSION 4
 int dj_abi_version(void);
 
-/* Storage type of a tensor in HBM.  Everything is fp32 unless an entry point's name ends in `_t`: those take, next to
- * each ACTIVATION / GRADIENT tensor, one of these codes (BASELINE config 5, "fp16-input / fp32-accumulate": under
+/* Storage type of a tensor in HBM, passed next to each ACTIVATION / GRADIENT tensor: the `dt_*` fields of the convolution
+ * argument structs, and the `dt_*` arguments of the elementwise entry points whose name ends in `_t`.
+ * Everything is fp32 unless such a code says otherwise (BASELINE config 5, "fp16-input / fp32-accumulate": under
  * K.set_floatx('float16') the backbone's conv outputs and block sums are held as fp16, their gradients as bf16 -- the
  * exponent range gradients need --; weights, their gradients, the optimizer state, BatchNormalization statistics and all
- * arithmetic outside the MFMA operands stay fp32).  `ld_*` are in ELEMENTS of the tensor they describe. */
+ * arithmetic outside the MFMA operands stay fp32).  `ld_*` are in ELEMENTS of the tensor they describe.
+ * In the three convolution GEMMs 16-bit tensors exist in arithmetic mode 1 only; a 16-bit operand needs the branch-free
+ * kernel's preconditions (channel counts that are multiples of 32, 16-byte aligned bases, stride-1 or 1x1 input gradients)
+ * and is an error otherwise -- never a silent conversion pass.  A 16-bit RESULT is written by one K range: such a launch is
+ * never split over workgroups, whatever the tuner registered. */
 #define DJ_F32 0
 #define DJ_F16 1
 #define DJ_BF16 2
@@ -69,97 +75,13 @@ typedef struct dj_conv2d_desc {
  * pixels, independent of the tile configuration. */
 int dj_conv2d_fwd_stats_rows(const dj_conv2d_desc* d);
 
-/* y = act(conv(pro(x), w) + bias).  Replaces Conv2D.call (TF conv2d + bias_add [+ relu]).
- *   pro_scale/pro_shift ([in_c], optional): x is read as x*scale+shift (then ReLU if
- *     pro_relu) on in-bounds pixels only -- the BatchNormalization+Activation that Keras
- *     runs between two convs (L/models/...resnet.py:80-81,90-91) folded into the load.
- *   stats (optional): per-row-tile column sums / sums of squares of conv(x,w) WITHOUT bias,
- *     consumed by dj_bn_finalize (training-mode BatchNormalization statistics). */
-/* `relu` argument of dj_conv2d_nhwc_fwd: DJ_CONV_RELU = fused ReLU epilogue; DJ_CONV_Y_ZEROED = the caller guarantees y is
- * all zeros on entry, so a split-K launch (atomic accumulation) does not clear it first. */
-#define DJ_CONV_RELU 1
-#define DJ_CONV_Y_ZEROED 2
-#define DJ_CONV_STATS_MAY_SPLIT 4 /* dj_conv2d_nhwc_fwd_ws only, see there */
-int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                       float* y, const float* pro_scale, const float* pro_shift, int pro_relu,
-                       int relu, float* stats, void* stream);
-
-/* dj_conv2d_nhwc_fwd with a caller-owned workspace (the reference's TF convolution is bit-reproducible in the forward
- * pass, L/models/keras_ssd300_dct_j2d_resnet.py:481-675 are the small-map layers this matters for): when the tuned
- * launch splits its reduction over workgroups and `workspace_floats` >= dj_conv2d_fwd_workspace_floats(d, ...), the K
- * chunks store their partial tiles to the workspace and a second kernel adds them in a fixed order, adds the bias,
- * applies ReLU and -- if `stats` is given -- takes the BatchNormalization statistics of the sum; without (enough)
- * workspace the launch accumulates with fp32 atomics in arrival order like dj_conv2d_nhwc_fwd.
- * DJ_CONV_STATS_MAY_SPLIT in `relu`: a launch with `stats` is tuned like one without and may be split (its statistics
- * then come from the reduction); otherwise a launch with `stats` is never split. */
-int dj_conv2d_nhwc_fwd_ws(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                          float* y, const float* pro_scale, const float* pro_shift, int pro_relu,
-                          int relu, float* stats, float* workspace, long workspace_floats, void* stream);
-/* floats of workspace that make the CURRENT tuning choice for this geometry run without atomics (0: not split; < 0: bad
- * descriptor) */
-long dj_conv2d_fwd_workspace_floats(const dj_conv2d_desc* d, int may_split_stats);
-
-/* dx (+)= conv_transpose(dy, w) [+ bias].  Gradient of Conv2D w.r.t. its input (TF
- * Conv2DBackpropInput); with `bias` it is also the forward of keras.layers.Conv2DTranspose
- * (L/models/...resnet.py:1709-1711), whose (kh,kw,out,in) kernel is the HWIO kernel of
- * the convolution it transposes.  beta: bit 0 = accumulate into dx; DJ_DGRAD_NO_SPLIT = never split the reduction over
- * workgroups (a split launch adds with fp32 atomics in arrival order; the forward use as Conv2DTranspose sets it so that
- * the forward pass stays bit-reproducible). */
-#define DJ_DGRAD_NO_SPLIT 2
-int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias,
-                         float* dx, int beta, void* stream);
-/* Input gradient + the BatchNormalization BACKWARD statistics of the tensor it produces, in one launch.  dx here is
- * g = dL/d relu(bn(z)) for the BatchNormalization layer whose ONLY consumer is this convolution
- * (L/models/keras_ssd300_dct_j2d_resnet.py:77-96: conv -> BatchNormalization -> Activation('relu') -> conv inside the
- * bottleneck blocks); z [batch*in_h*in_w][ld_z] is that layer's input, mean / invstd its saved batch statistics, scale /
- * shift its affine (both NULL: no ReLU behind it, nothing is masked).  Besides storing dx the epilogue writes
- *   partial[r][0][c] = sum g_m,   partial[r][1][c] = sum g_m * (z - mean[c]) * invstd[c],   g_m = g where z*scale+shift > 0
- * over rows 64 r .. 64 r + 63, partial = [ceil(batch*in_h*in_w / 64)][2][in_c]: what dj_bn_bwd_reduce(mask_mode 2 / 0)
- * computes in a pass of its own over g and z, in the layout dj_bn_bwd_finalize reads.  Never split over K, never
- * accumulating; not for strided 1x1 convolutions (their dx is scattered). */
-int dj_conv2d_nhwc_dgrad_bnbwd(const dj_conv2d_desc* d, const float* dy, const float* w, float* dx, const float* z, int ld_z,
-                               const float* mean, const float* invstd, const float* scale, const float* shift,
-                               float* partial, void* stream);
-/* Input gradient whose epilogue also applies the ReLU mask of the tensor it differentiates:
- *   dx[m][c] = mask_x[m][c] > 0 ? conv_transpose(dy, w)[m][c] (+ bias[c]) (+ dx[m][c] when beta) : 0
- * mask_x [batch*in_h*in_w][ld_mask] is the convolution's own forward input x = relu(Add(...)) -- the output of a residual
- * block (L/models/keras_ssd300_dct_j2d_resnet.py:96-99).  When this launch is the LAST writer of that block's output
- * gradient, the gradient is masked once, where it is completed: the BatchNormalization backward passes of the block read
- * it unmasked-mode (mask_mode 0, no read of x) and an identity shortcut shares the buffer.  Exactly the values of
- * dj_conv2d_nhwc_dgrad(beta) followed by dj_relu_bwd in place.  One K range per tile: DJ_ERR_ARG when the tuning entry of
- * direction 1 registers a split reduction, for the strided 1x1 scatter form and in the 16-bit arithmetic modes (fp32
- * tensors only); dj_conv2d_dgrad_relumask_supported() != 0 says beforehand that none of these applies.  Takes the tile
- * variant of direction 1's tuning entry; geometries outside the branch-free kernels' preconditions run the generic kernel. */
-int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d);
-int dj_conv2d_nhwc_dgrad_relumask(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias, float* dx,
-                                  int beta, const float* mask_x, int ld_mask, void* stream);
-
-/* Residual Add + ReLU evaluated inside the consumer (the first 1x1 conv of the next bottleneck block,
- * L/models/keras_ssd300_dct_j2d_resnet.py:96-99 then :66-68): the conv's input is
- *   a[m][c] = relu(x[m][c]*pro_scale[c] + pro_shift[c] + res[m][c]*res_scale[c] + res_shift[c])
- * (res_scale/res_shift NULL: res taken as is -- an identity shortcut), computed while the A tile is staged; when
- * sum_out != NULL the tensor `a` -- the output of Add()+Activation('relu') that later layers and the backward pass
- * read -- is stored there by the same launch.  Only for 1x1, stride-1, unpadded convs with in_c % 32 == 0
- * (dj_conv2d_fwd_addrelu_supported() != 0); any other geometry is an error, never a silent slow path. */
-int dj_conv2d_fwd_addrelu_supported(const dj_conv2d_desc* d);
-int dj_conv2d_nhwc_fwd_addrelu(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                               const float* pro_scale, const float* pro_shift, const float* res, int ld_res,
-                               const float* res_scale, const float* res_shift, float* sum_out, int ld_sum, int relu,
-                               float* stats, void* stream);
-/* ... with the split-K workspace of dj_conv2d_nhwc_fwd_ws (same rules, same size query) */
-int dj_conv2d_nhwc_fwd_addrelu_ws(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                                  const float* pro_scale, const float* pro_shift, const float* res, int ld_res,
-                                  const float* res_scale, const float* res_shift, float* sum_out, int ld_sum, int relu,
-                                  float* stats, float* workspace, long workspace_floats, void* stream);
-
-/* Convolution + the training-mode BatchNormalization that follows it (keras BatchNormalization(axis=3) after Conv2D,
- * L/models/keras_ssd300_dct_j2d_resnet.py:66-99): the conv epilogue adds each tile's column sums / sums of squares to
- * `acc` with fp64 atomics, the workgroup that finishes last turns them into scale = gamma/sqrt(var+eps),
- * shift = beta - mean*scale, save_mean / save_invstd (for the backward pass) and the momentum update of the moving
- * statistics (Bessel-corrected variance), and leaves acc / ticket zero again.  Replaces conv `stats` +
- * dj_bn_train_finalize: no launch between the conv and its consumer.  `acc` = DJ_BN_ACC_REPLICAS*2*out_c doubles and
- * `ticket` = one unsigned, zero before the first launch.  res != NULL selects the residual-add prologue of
- * dj_conv2d_nhwc_fwd_addrelu. */
+/* y = act(conv(pro(x), w) + bias).  Replaces Conv2D.call (TF conv2d + bias_add [+ relu]).  One entry point; an all-zero
+ * dj_conv_fwd_args means fp32 tensors and no option, and an option is selected by its pointer.
+ * Keras call sites: L/models/keras_ssd300_dct_j2d_resnet.py:77-99,128-163. */
+#define DJ_CONV_RELU 1            /* fused ReLU epilogue */
+#define DJ_CONV_Y_ZEROED 2        /* y is all zeros on entry: a split-K launch (atomic accumulation) does not clear it first */
+#define DJ_CONV_STATS_MAY_SPLIT 4 /* with `workspace`: a launch with `stats` is tuned like one without and may be split (its
+                                   * statistics then come from the reduction); otherwise a launch with `stats` is never split */
 #define DJ_BN_ACC_REPLICAS 16
 typedef struct dj_bn_train {
   double* acc;
@@ -174,10 +96,117 @@ typedef struct dj_bn_train {
   float* save_invstd;
   float eps, momentum;
 } dj_bn_train;
-int dj_conv2d_nhwc_fwd_bn(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                          const float* pro_scale, const float* pro_shift, int pro_relu, const float* res, int ld_res,
-                          const float* res_scale, const float* res_shift, float* sum_out, int ld_sum,
-                          const dj_bn_train* bn, void* stream);
+typedef struct dj_conv_fwd_args {
+  /* operands: x fp32 | fp16; w the fp32 master weights or their fp16 shadow (dj_shadow_weights); y fp32 | fp16 (rounded
+   * AFTER the fp32 bias / ReLU / statistics epilogue) */
+  const void* x;
+  int dt_x;
+  const void* w;
+  int dt_w;
+  const float* bias; /* optional */
+  void* y;
+  int dt_y;
+  /* pro_scale / pro_shift ([in_c], optional, together): x is read as x*scale+shift (then ReLU if pro_relu) on in-bounds
+   * pixels only -- the BatchNormalization+Activation that Keras runs between two convs (L/models/...resnet.py:80-81,90-91)
+   * folded into the load */
+  const float* pro_scale;
+  const float* pro_shift;
+  int pro_relu;
+  int flags; /* DJ_CONV_RELU | DJ_CONV_Y_ZEROED | DJ_CONV_STATS_MAY_SPLIT */
+  /* optional, [dj_conv2d_fwd_stats_rows(d)][2][out_c]: per-row-tile column sums / sums of squares of conv(x,w) WITHOUT
+   * bias, consumed by dj_bn_train_finalize (training-mode BatchNormalization statistics) */
+  float* stats;
+  /* res != NULL: residual Add + ReLU evaluated inside the consumer (the first 1x1 conv of the next bottleneck block,
+   * L/models/keras_ssd300_dct_j2d_resnet.py:96-99 then :66-68): the conv's input is
+   *   a[m][c] = relu(x[m][c]*pro_scale[c] + pro_shift[c] + res[m][c]*res_scale[c] + res_shift[c])
+   * (res_scale/res_shift NULL: res taken as is -- an identity shortcut; pro_scale/pro_shift are required and pro_relu is
+   * taken as 1; res has x's storage type), computed while the A tile is staged; when sum_out != NULL (fp32 | fp16,
+   * dt_sum) the tensor `a` -- the output of Add()+Activation('relu') that later layers and the backward pass read -- is
+   * stored there by the same launch.  Only for 1x1, stride-1, unpadded convs with in_c % 32 == 0
+   * (dj_conv2d_fwd_addrelu_supported() != 0); any other geometry is an error, never a silent slow path. */
+  const void* res;
+  int ld_res;
+  const float* res_scale;
+  const float* res_shift;
+  void* sum_out;
+  int ld_sum;
+  int dt_sum;
+  /* workspace != NULL: a caller-owned workspace (the reference's TF convolution is bit-reproducible in the forward pass,
+   * L/models/keras_ssd300_dct_j2d_resnet.py:481-675 are the small-map layers this matters for): when the tuned launch
+   * splits its reduction over workgroups and workspace_floats >= dj_conv2d_fwd_workspace_floats(d, ...), the K chunks
+   * store their partial tiles to the workspace and a second kernel adds them in a fixed order, adds the bias, applies
+   * ReLU and -- if `stats` is given -- takes the BatchNormalization statistics of the sum; without (enough) workspace a
+   * split launch accumulates with fp32 atomics in arrival order. */
+  float* workspace;
+  long workspace_floats;
+  /* bn != NULL: convolution + the training-mode BatchNormalization that follows it (keras BatchNormalization(axis=3)
+   * after Conv2D, L/models/keras_ssd300_dct_j2d_resnet.py:66-99): the conv epilogue adds each tile's column sums / sums of
+   * squares to bn->acc with fp64 atomics, the workgroup that finishes last turns them into scale = gamma/sqrt(var+eps),
+   * shift = beta - mean*scale, save_mean / save_invstd (for the backward pass) and the momentum update of the moving
+   * statistics (Bessel-corrected variance), and leaves acc / ticket zero again.  Replaces `stats` +
+   * dj_bn_train_finalize: no launch between the conv and its consumer.  acc = DJ_BN_ACC_REPLICAS*2*out_c doubles and
+   * ticket = one unsigned, zero before the first launch.  fp32 tensors only; no `stats`, no DJ_CONV_RELU. */
+  const dj_bn_train* bn;
+} dj_conv_fwd_args;
+int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_args* a, void* stream);
+/* floats of workspace that make the CURRENT tuning choice for this geometry run without atomics (0: not split; < 0: bad
+ * descriptor) */
+long dj_conv2d_fwd_workspace_floats(const dj_conv2d_desc* d, int may_split_stats);
+int dj_conv2d_fwd_addrelu_supported(const dj_conv2d_desc* d);
+
+/* dx (+)= conv_transpose(dy, w) [+ bias].  Gradient of Conv2D w.r.t. its input (TF
+ * Conv2DBackpropInput); with `bias` it is also the forward of keras.layers.Conv2DTranspose
+ * (L/models/...resnet.py:1709-1711), whose (kh,kw,out,in) kernel is the HWIO kernel of
+ * the convolution it transposes.  An all-zero dj_conv_dgrad_args means fp32 tensors and no option. */
+#define DJ_DGRAD_NO_SPLIT 2
+typedef struct dj_conv_dgrad_args {
+  /* operands: dy fp32 | bf16; w the fp32 master weights or their bf16 shadow (dj_shadow_weights); dx any type (bf16 for
+   * the gradient of a fp16 activation; accumulates in that type when flags & 1) */
+  const void* dy;
+  int dt_dy;
+  const void* w;
+  int dt_w;
+  const float* bias; /* optional */
+  void* dx;
+  int dt_dx;
+  /* bit 0 = accumulate into dx; DJ_DGRAD_NO_SPLIT = never split the reduction over workgroups (a split launch adds with
+   * fp32 atomics in arrival order; the forward use as Conv2DTranspose sets it so that the forward pass stays
+   * bit-reproducible) */
+  int flags;
+  /* partial != NULL: the BatchNormalization BACKWARD statistics of the tensor this launch produces.  dx is then
+   * g = dL/d relu(bn(z)) for the BatchNormalization layer whose ONLY consumer is this convolution
+   * (L/models/keras_ssd300_dct_j2d_resnet.py:77-96: conv -> BatchNormalization -> Activation('relu') -> conv inside the
+   * bottleneck blocks); z [batch*in_h*in_w][ld_z] (fp32 | fp16, required) is that layer's input, mean / invstd (required)
+   * its saved batch statistics, scale / shift its affine (both NULL: no ReLU behind it, nothing is masked).  Besides
+   * storing dx the epilogue writes
+   *   partial[r][0][c] = sum g_m,   partial[r][1][c] = sum g_m * (z - mean[c]) * invstd[c],   g_m = g where z*scale+shift > 0
+   * over rows 64 r .. 64 r + 63, partial = [ceil(batch*in_h*in_w / 64)][2][in_c]: what dj_bn_bwd_reduce(mask_mode 2 / 0)
+   * computes in a pass of its own over g and z, in the layout dj_bn_bwd_finalize reads.  One K range per tile; `bias` and
+   * the accumulate bit are errors; not for strided 1x1 convolutions (their dx is scattered). */
+  const void* z;
+  int ld_z;
+  int dt_z;
+  const float* mean;
+  const float* invstd;
+  const float* scale;
+  const float* shift;
+  float* partial;
+  /* mask_x != NULL: the epilogue also applies the ReLU mask of the tensor it differentiates:
+   *   dx[m][c] = mask_x[m][c] > 0 ? conv_transpose(dy, w)[m][c] (+ bias[c]) (+ dx[m][c] when flags & 1) : 0
+   * mask_x [batch*in_h*in_w][ld_mask] is the convolution's own forward input x = relu(Add(...)) -- the output of a
+   * residual block (L/models/keras_ssd300_dct_j2d_resnet.py:96-99).  When this launch is the LAST writer of that block's
+   * output gradient, the gradient is masked once, where it is completed: the BatchNormalization backward passes of the
+   * block read it unmasked-mode (mask_mode 0, no read of x) and an identity shortcut shares the buffer.  Exactly the
+   * values of a plain launch followed by dj_relu_bwd in place.  One K range per tile: DJ_ERR_ARG when the tuning entry of
+   * direction 1 registers a split reduction, for the strided 1x1 scatter form, in the 16-bit arithmetic modes (fp32
+   * tensors only) and together with `partial`; dj_conv2d_dgrad_relumask_supported() != 0 says beforehand that none of
+   * the first three applies.  Takes the tile variant of direction 1's tuning entry; geometries outside the branch-free
+   * kernels' preconditions run the generic kernel. */
+  const float* mask_x;
+  int ld_mask;
+} dj_conv_dgrad_args;
+int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const dj_conv_dgrad_args* a, void* stream);
+int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d);
 
 /* Debug/test switch: 0 forces the generic (branchy, any-shape) implicit-GEMM kernel, 1 (default) lets the
  * launcher pick the branch-free buffer-load kernel whenever its alignment preconditions hold. */
@@ -209,7 +238,7 @@ int dj_set_thread_compute_mode(int mode);
 int dj_get_compute_mode(void);
 
 /* Launch-configuration overrides per conv geometry, filled by the plan-time autotuner: `dir` 0 fwd, 1 dgrad,
- * 2 wgrad (+4: forward that takes BN statistics; 9: the input gradient of dj_conv2d_nhwc_dgrad_bnbwd, which runs other
+ * 2 wgrad (+4: forward that takes BN statistics; 9: the input gradient that takes BN backward statistics (`partial`), which runs other
  * kernels than a plain input gradient and is never split -- without an entry of its own it takes the tile shape of the
  * dir-1 entry); cfg in [0, dj_conv2d_tune_configs()) selects the tile shape
  * (128x128, 128x64, 64x64, 128x32) and schedule variant -- in mode 0 the count is twice that of the other modes, the upper
@@ -218,36 +247,26 @@ int dj_conv2d_tune_configs(void);
 int dj_conv2d_tune_set(int dir, const dj_conv2d_desc* d, int cfg, int splits);
 int dj_conv2d_default_config(int dir, const dj_conv2d_desc* d, int* cfg, int* splits);
 
-/* dw = sum over pixels pro(x)^T dy  (TF Conv2DBackpropFilter).  dw is HWIO, overwritten.  The pixel reduction is
- * split over workgroups that accumulate with fp32 atomics; `dw_zeroed` = 1 promises dw already holds zeros (the engine
- * clears its whole flat gradient buffer once per step instead of one memset per layer). */
-int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const float* x, const float* dy, float* dw,
-                         const float* pro_scale, const float* pro_shift, int pro_relu, int dw_zeroed, void* stream);
+/* dw = sum over pixels pro(x)^T dy  (TF Conv2DBackpropFilter).  dw is HWIO, overwritten: always the fp32 gradient of the
+ * master weights.  The pixel reduction is split over workgroups that accumulate with fp32 atomics. */
+typedef struct dj_conv_wgrad_args {
+  const void* x;  /* fp32 | fp16 */
+  int dt_x;
+  const void* dy; /* fp32 | bf16 */
+  int dt_dy;
+  float* dw;
+  const float* pro_scale; /* as in dj_conv_fwd_args */
+  const float* pro_shift;
+  int pro_relu;
+  int dw_zeroed; /* 1 promises dw already holds zeros (the engine clears its whole flat gradient buffer once per step
+                  * instead of one memset per layer) */
+} dj_conv_wgrad_args;
+int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const dj_conv_wgrad_args* a, void* stream);
 
-/* ---- the three convolution GEMMs over tensors that carry their storage type (arithmetic mode 1 only) ----
- * Same semantics as the float entry points they generalise; a 16-bit operand needs the branch-free kernel's
- * preconditions (channel counts that are multiples of 32, 16-byte aligned bases, stride-1 or 1x1 input gradients) and is an
- * error otherwise -- never a silent conversion pass.  A 16-bit RESULT is written by one K range: such a launch is never
- * split over workgroups, whatever the tuner registered.
- * dj_conv2d_nhwc_fwd_t = dj_conv2d_nhwc_fwd_ws (res == NULL) / dj_conv2d_nhwc_fwd_addrelu_ws (res != NULL: then pro_relu is
- * ignored, the residual operand has x's type): x, res fp32 | fp16; y fp32 | fp16 (rounded AFTER the fp32 bias / ReLU /
- * statistics epilogue); sum_out fp32 | fp16.  Keras call sites: L/models/keras_ssd300_dct_j2d_resnet.py:77-99,128-163. */
-int dj_conv2d_nhwc_fwd_t(const dj_conv2d_desc* d, const void* x, int dt_x, const void* w, int dt_w, const float* bias, void* y,
-                         int dt_y, const float* pro_scale, const float* pro_shift, int pro_relu, int relu, float* stats,
-                         const void* res, int ld_res, const float* res_scale, const float* res_shift, void* sum_out,
-                         int ld_sum, int dt_sum, float* workspace, long workspace_floats, void* stream);
-/* dj_conv2d_nhwc_dgrad (z == NULL) / dj_conv2d_nhwc_dgrad_bnbwd (z != NULL: beta must be 0, bias NULL): dy fp32 | bf16,
- * dx any type (bf16 for the gradient of a fp16 activation; accumulates in that type when beta & 1), z fp32 | fp16. */
-int dj_conv2d_nhwc_dgrad_t(const dj_conv2d_desc* d, const void* dy, int dt_dy, const void* w, int dt_w, const float* bias,
-                           void* dx, int dt_dx, int beta, const void* z, int ld_z, int dt_z, const float* mean, const float* invstd,
-                           const float* scale, const float* shift, float* partial, void* stream);
-/* `w` of the two entry points above: the fp32 master weights, or their 16-bit shadow in the type the GEMM multiplies in
- * (fp16 forward, bf16 input gradient), refreshed once per step by dj_shadow_weights: w16[i] = fp16(w[i]) and / or
- * wbf[i] = bf16(w[i]) for i < n (n a multiple of 4; either output may be NULL). */
+/* `w` of the forward and input-gradient GEMMs: the fp32 master weights, or their 16-bit shadow in the type the GEMM
+ * multiplies in (fp16 forward, bf16 input gradient), refreshed once per step by dj_shadow_weights: w16[i] = fp16(w[i]) and /
+ * or wbf[i] = bf16(w[i]) for i < n (n a multiple of 4; either output may be NULL). */
 int dj_shadow_weights(const float* w, void* w16, void* wbf, long n, void* stream);
-/* dj_conv2d_nhwc_wgrad: x fp32 | fp16, dy fp32 | bf16; dw is the fp32 gradient of the master weights. */
-int dj_conv2d_nhwc_wgrad_t(const dj_conv2d_desc* d, const void* x, int dt_x, const void* dy, int dt_dy, float* dw,
-                           const float* pro_scale, const float* pro_shift, int pro_relu, int dw_zeroed, void* stream);
 
 /* ---- blocked column reductions (two-stage, deterministic) ------------------------- */
 /* Rows of the `partial` buffers written by the *_partial / *_reduce entry points for a

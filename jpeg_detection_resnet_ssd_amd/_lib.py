@@ -65,8 +65,29 @@ class ConvDesc(Structure):
         "pad_top", "pad_left", "ld_x", "ld_y")]
 
 
+_P, _I = c_void_p, c_int
+
+
+class ConvFwdArgs(Structure):   # dj_conv_fwd_args: all zeros = fp32 tensors, no option
+    _fields_ = [("x", _P), ("dt_x", _I), ("w", _P), ("dt_w", _I), ("bias", _P), ("y", _P), ("dt_y", _I),
+                ("pro_scale", _P), ("pro_shift", _P), ("pro_relu", _I), ("flags", _I), ("stats", _P),
+                ("res", _P), ("ld_res", _I), ("res_scale", _P), ("res_shift", _P), ("sum_out", _P), ("ld_sum", _I),
+                ("dt_sum", _I), ("workspace", _P), ("workspace_floats", c_long), ("bn", POINTER(BnTrain))]
+
+
+class ConvDgradArgs(Structure):   # dj_conv_dgrad_args
+    _fields_ = [("dy", _P), ("dt_dy", _I), ("w", _P), ("dt_w", _I), ("bias", _P), ("dx", _P), ("dt_dx", _I), ("flags", _I),
+                ("z", _P), ("ld_z", _I), ("dt_z", _I), ("mean", _P), ("invstd", _P), ("scale", _P), ("shift", _P),
+                ("partial", _P), ("mask_x", _P), ("ld_mask", _I)]
+
+
+class ConvWgradArgs(Structure):   # dj_conv_wgrad_args
+    _fields_ = [("x", _P), ("dt_x", _I), ("dy", _P), ("dt_dy", _I), ("dw", _P), ("pro_scale", _P), ("pro_shift", _P),
+                ("pro_relu", _I), ("dw_zeroed", _I)]
+
+
 _lib = None
-ABI_VERSION = 3     # DJ_ABI_VERSION of include/dj_hip.h these bindings were written for
+ABI_VERSION = 4     # DJ_ABI_VERSION of include/dj_hip.h these bindings were written for
 
 
 def load():
@@ -101,20 +122,12 @@ SIGNATURES = {
     "dj_last_error": (c_char_p, []),
     "dj_abi_version": (c_int, []),
     "dj_conv2d_fwd_stats_rows": (c_int, [POINTER(ConvDesc)]),
-    "dj_conv2d_nhwc_fwd": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, c_int, c_int, FP, c_void_p]),
-    "dj_conv2d_nhwc_fwd_ws": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, c_int, c_int, FP, FP, c_long, c_void_p]),
+    "dj_conv2d_nhwc_fwd": (c_int, [POINTER(ConvDesc), POINTER(ConvFwdArgs), c_void_p]),
     "dj_conv2d_fwd_workspace_floats": (c_long, [POINTER(ConvDesc), c_int]),
-    "dj_conv2d_nhwc_dgrad": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, c_int, c_void_p]),
-    "dj_conv2d_nhwc_dgrad_bnbwd": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, c_int, FP, FP, FP, FP, FP, c_void_p]),
+    "dj_conv2d_nhwc_dgrad": (c_int, [POINTER(ConvDesc), POINTER(ConvDgradArgs), c_void_p]),
     "dj_conv2d_dgrad_relumask_supported": (c_int, [POINTER(ConvDesc)]),
-    "dj_conv2d_nhwc_dgrad_relumask": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, c_int, FP, c_int, c_void_p]),
-    "dj_conv2d_nhwc_wgrad": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, c_int, c_int, c_void_p]),
-    "dj_conv2d_nhwc_fwd_t": (c_int, [POINTER(ConvDesc), FP, c_int, FP, c_int, FP, FP, c_int, FP, FP, c_int, c_int, FP, FP, c_int, FP,
-                                     FP, FP, c_int, c_int, FP, c_long, c_void_p]),
-    "dj_conv2d_nhwc_dgrad_t": (c_int, [POINTER(ConvDesc), FP, c_int, FP, c_int, FP, FP, c_int, c_int, FP, c_int, c_int, FP, FP, FP,
-                                       FP, FP, c_void_p]),
+    "dj_conv2d_nhwc_wgrad": (c_int, [POINTER(ConvDesc), POINTER(ConvWgradArgs), c_void_p]),
     "dj_shadow_weights": (c_int, [FP, FP, FP, c_long, c_void_p]),
-    "dj_conv2d_nhwc_wgrad_t": (c_int, [POINTER(ConvDesc), FP, c_int, FP, c_int, FP, FP, FP, c_int, c_int, c_void_p]),
     "dj_affine_act_t": (c_int, [FP, c_int, c_int, FP, FP, FP, c_int, c_int, FP, FP, FP, c_int, c_int, c_long, c_int, c_int,
                                 c_void_p]),
     "dj_bn_bwd_reduce_t": (c_int, [FP, c_int, c_int, FP, c_int, c_int, FP, c_int, c_int, FP, FP, FP, FP, c_int, c_long, c_int, FP,
@@ -124,15 +137,9 @@ SIGNATURES = {
     "dj_relu_bwd_t": (c_int, [FP, c_int, c_int, FP, c_int, c_int, FP, c_int, c_int, c_long, c_int, c_int, c_void_p]),
     "dj_copy2d_t": (c_int, [FP, c_int, c_long, FP, c_int, c_long, c_long, c_long, c_int, c_void_p]),
     "dj_conv2d_fwd_addrelu_supported": (c_int, [POINTER(ConvDesc)]),
-    "dj_conv2d_nhwc_fwd_addrelu": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, FP, c_int, FP, FP, FP, c_int, c_int, FP,
-                                           c_void_p]),
-    "dj_conv2d_nhwc_fwd_addrelu_ws": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, FP, c_int, FP, FP, FP, c_int, c_int,
-                                              FP, FP, c_long, c_void_p]),
     "dj_colsum_direct": (c_int, [FP, c_long, c_int, c_int, FP, c_int, c_void_p]),
     "dj_colsum_multi": (c_int, [POINTER(ColsumPart), c_int, c_void_p]),
     "dj_copy2d_multi": (c_int, [POINTER(CopyPart), c_int, c_void_p]),
-    "dj_conv2d_nhwc_fwd_bn": (c_int, [POINTER(ConvDesc), FP, FP, FP, FP, FP, FP, c_int, FP, c_int, FP, FP, FP, c_int,
-                                      POINTER(BnTrain), c_void_p]),
     "dj_set_fast_path": (None, [c_int]),
     "dj_set_gather_variants": (None, [c_int]),
     "dj_set_compute_mode": (c_int, [c_int]),

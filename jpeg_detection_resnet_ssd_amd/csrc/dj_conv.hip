@@ -126,7 +126,7 @@ static bool tune_lookup(int dir, const dj_conv2d_desc* d, int* cfg, int* splits)
 extern "C" int dj_conv2d_tune_configs(void) { return dj_compute_mode() == 0 ? 2 * N_CFG : N_CFG; }
 
 // dir: 0 fwd, 1 dgrad, 2 wgrad, +4 when the forward takes BN statistics, 9 = input gradient that takes the
-// BatchNormalization backward statistics (dj_conv2d_nhwc_dgrad_bnbwd).  cfg < 0 removes the override.
+// BatchNormalization backward statistics (dj_conv_dgrad_args.partial).  cfg < 0 removes the override.
 extern "C" int dj_conv2d_tune_set(int dir, const dj_conv2d_desc* d, int cfg, int splits) {
   DJ_CHECK_ARG(d != nullptr && cfg < (dj_compute_mode() == 0 ? 2 * N_CFG : N_CFG) && splits >= 1, "tune_set: bad arguments");
   std::lock_guard<std::mutex> g(g_tune_mu);
@@ -180,7 +180,7 @@ static int extent_bytes(long pixels, long ld, long c, int es = 4) {
   return (b > 0 && b < 0x7FFFFFF0L) ? (int)b : 0;
 }
 
-// storage types of the tensors of a launch (DJ_F32 / DJ_F16 / DJ_BF16); the float entry points pass all zeros
+// storage types of the tensors of a launch (DJ_F32 / DJ_F16 / DJ_BF16)
 static inline int dt_size(int dt) { return dt == DJ_F32 ? 4 : 2; }
 static inline bool dt_ok(int dt) { return dt == DJ_F32 || dt == DJ_F16 || dt == DJ_BF16; }
 
@@ -305,44 +305,68 @@ static int launch_splitk_reduce(const float* slabs, int nsplit, long slab_stride
   return DJ_OK;
 }
 
-struct FwdResidual {
-  const dj_bn_train* bn = nullptr;   // finish the following BatchNormalization inside the launch
-  const float* res = nullptr;
-  int ld_res = 0;
-  const float* res_scale = nullptr;
-  const float* res_shift = nullptr;
-  float* sum_out = nullptr;
-  int ld_sum = 0;
-};
+// *kchunk = the K range of one split, a multiple of DJ_BK; -> the number of splits that are not empty
+static int split_k(int K, int splits, int* kchunk) {
+  *kchunk = dj_cdiv(dj_cdiv(K, splits), DJ_BK) * DJ_BK;
+  return dj_cdiv(K, *kchunk);
+}
 
-struct FwdTypes {   // how x (and the residual operand), the weights, y and the stored residual sum are held in HBM
-  int x = DJ_F32, w = DJ_F32, y = DJ_F32, sum = DJ_F32;
-};
+// the memsets in front of a launch that accumulates with atomics (or scatters)
+static int memset_status(hipError_t e, const char* what) {
+  if (e == hipSuccess) return DJ_OK;
+  dj_set_error("%s: memset: %s", what, hipGetErrorString(e));
+  return DJ_ERR_HIP;
+}
+static int clear_rows(void* t, long rows, int cols, int ld, int es, hipStream_t s, const char* what) {
+  return memset_status(hipMemset2DAsync(t, (size_t)ld * es, 0, (size_t)cols * es, (size_t)rows, s), what);
+}
 
-static int conv_fwd_impl(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                         const float* pro_scale, const float* pro_shift, int pro_relu, int relu, float* stats,
-                         const FwdResidual& rz, void* stream, float* ws = nullptr, long ws_floats = 0,
-                         const FwdTypes& ty = FwdTypes()) {
+extern "C" int dj_conv2d_fwd_addrelu_supported(const dj_conv2d_desc* d) {
+  if (check_desc(d)) return 0;
+  return d->kernel_h == 1 && d->kernel_w == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_top == 0 &&
+         d->pad_left == 0 && d->in_h == d->out_h && d->in_w == d->out_w && d->in_c % 32 == 0 && d->ld_x % 4 == 0 &&
+         d->out_c % 4 == 0;
+}
+
+extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_args* args, void* stream) {
+  DJ_CHECK_ARG(args != nullptr, "conv fwd: null argument struct");
+  const dj_conv_fwd_args& a = *args;
+  DJ_CHECK_ARG(dt_ok(a.dt_x) && dt_ok(a.dt_w) && dt_ok(a.dt_y) && dt_ok(a.dt_sum), "conv fwd: unknown storage type");
+  DJ_CHECK_ARG(a.workspace_floats >= 0 && (a.workspace != nullptr || a.workspace_floats == 0), "conv fwd: bad workspace");
+  DJ_CHECK_ARG(a.res || !a.sum_out, "conv fwd: sum_out without res");
+  if (a.res) {
+    DJ_CHECK_ARG(d && dj_conv2d_fwd_addrelu_supported(d), "conv fwd (residual add): needs a 1x1 stride-1 unpadded conv with "
+                                                           "in_c %% 32 == 0");
+    DJ_CHECK_ARG(a.pro_scale && a.pro_shift, "conv fwd (residual add): pro_scale and pro_shift are required");
+    DJ_CHECK_ARG((a.res_scale == nullptr) == (a.res_shift == nullptr), "conv fwd (residual add): res_scale/res_shift come together");
+    DJ_CHECK_ARG(a.ld_res >= d->in_c && a.ld_res % 4 == 0 && (!a.sum_out || (a.ld_sum >= d->in_c && a.ld_sum % 4 == 0)),
+                 "conv fwd (residual add): bad ld_res / ld_sum");
+    DJ_CHECK_ARG(aligned16(a.res) && aligned16(a.sum_out) && aligned16(a.res_scale) && aligned16(a.res_shift),
+                 "conv fwd (residual add): tensors must be 16-byte aligned");
+  }
   if (int rc = check_desc(d)) return rc;
-  DJ_CHECK_ARG(x && w && y, "conv fwd: null tensor");
-  const bool io16 = ty.x != DJ_F32 || ty.y != DJ_F32 || ty.sum != DJ_F32 || ty.w != DJ_F32;
-  DJ_CHECK_ARG((ty.x == DJ_F32 || ty.x == DJ_F16) && (ty.y == DJ_F32 || ty.y == DJ_F16) && (ty.sum == DJ_F32 || ty.sum == DJ_F16) &&
-                   (ty.w == DJ_F32 || ty.w == DJ_F16),
+  DJ_CHECK_ARG(a.x && a.w && a.y, "conv fwd: null tensor");
+  const int dt_sum = a.sum_out ? a.dt_sum : DJ_F32;
+  const bool io16 = a.dt_x != DJ_F32 || a.dt_y != DJ_F32 || dt_sum != DJ_F32 || a.dt_w != DJ_F32;
+  DJ_CHECK_ARG((a.dt_x == DJ_F32 || a.dt_x == DJ_F16) && (a.dt_y == DJ_F32 || a.dt_y == DJ_F16) &&
+                   (dt_sum == DJ_F32 || dt_sum == DJ_F16) && (a.dt_w == DJ_F32 || a.dt_w == DJ_F16),
                "conv fwd: activations and the weight shadow are held as fp32 or fp16");
-  DJ_CHECK_ARG(!io16 || (dj_compute_mode() == 1 && !rz.bn),
+  DJ_CHECK_ARG(!io16 || (dj_compute_mode() == 1 && !a.bn),
                "conv fwd: 16-bit tensors need arithmetic mode 1 (float16) and no in-kernel BatchNormalization finalize");
-  DJ_CHECK_ARG((pro_scale == nullptr) == (pro_shift == nullptr), "conv fwd: pro_scale/pro_shift must come together");
+  DJ_CHECK_ARG((a.pro_scale == nullptr) == (a.pro_shift == nullptr), "conv fwd: pro_scale/pro_shift must come together");
   hipStream_t s = (hipStream_t)stream;
+  float* const y = (float*)a.y;
+  float* const ws = a.workspace;
   DjIgemmParams p;
   memset(&p, 0, sizeof(p));
-  p.A = x;
-  p.B = w;
+  p.A = (const float*)a.x;
+  p.B = (const float*)a.w;
   p.C = y;
-  p.bias = bias;
-  p.pro_scale = pro_scale;
-  p.pro_shift = pro_shift;
-  p.pro_relu = pro_relu;
-  p.stats = stats;
+  p.bias = a.bias;
+  p.pro_scale = a.pro_scale;
+  p.pro_shift = a.pro_shift;
+  p.pro_relu = a.res ? 1 : a.pro_relu;
+  p.stats = a.stats;
   p.M = d->batch * d->out_h * d->out_w;
   p.N = d->out_c;
   p.K = d->kernel_h * d->kernel_w * d->in_c;
@@ -356,35 +380,35 @@ static int conv_fwd_impl(const dj_conv2d_desc* d, const float* x, const float* w
   p.ldb = d->out_c;
   p.ldc = d->ld_y;
   p.cmap = 0;
-  const bool y_zeroed = (relu & DJ_CONV_Y_ZEROED) != 0;
-  const bool stats_may_split = (relu & DJ_CONV_STATS_MAY_SPLIT) != 0 && stats != nullptr && ws != nullptr && !rz.bn;
-  relu &= DJ_CONV_RELU;
+  const bool y_zeroed = (a.flags & DJ_CONV_Y_ZEROED) != 0;
+  const bool stats_may_split = (a.flags & DJ_CONV_STATS_MAY_SPLIT) != 0 && a.stats != nullptr && ws != nullptr && !a.bn;
+  const int relu = a.flags & DJ_CONV_RELU;
   p.relu = relu;
-  p.vecA = (d->in_c % 4 == 0) && (d->ld_x % 4 == 0) && aligned_dt(x, ty.x) &&
-           (!pro_scale || (aligned16(pro_scale) && aligned16(pro_shift)));
-  p.vecB = (d->out_c % 4 == 0) && aligned_dt(w, ty.w);
-  p.a_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, d->ld_x, d->in_c, dt_size(ty.x));
-  p.a_dt = ty.x;
-  p.c_dt = ty.y;
-  p.sum_dt = ty.sum;
-  if (rz.res) {
-    p.A2 = rz.res;
-    p.ldsrc2 = rz.ld_res;
-    p.pro_scale2 = rz.res_scale;
-    p.pro_shift2 = rz.res_shift;
-    p.sum_out = rz.sum_out;
-    p.ld_sum = rz.ld_sum;
-    p.a2_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, rz.ld_res, d->in_c, dt_size(ty.x));
-    p.sum_bytes = rz.sum_out ? extent_bytes((long)d->batch * d->in_h * d->in_w, rz.ld_sum, d->in_c, dt_size(ty.sum)) : 0;
+  p.vecA = (d->in_c % 4 == 0) && (d->ld_x % 4 == 0) && aligned_dt(a.x, a.dt_x) &&
+           (!a.pro_scale || (aligned16(a.pro_scale) && aligned16(a.pro_shift)));
+  p.vecB = (d->out_c % 4 == 0) && aligned_dt(a.w, a.dt_w);
+  p.a_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, d->ld_x, d->in_c, dt_size(a.dt_x));
+  p.a_dt = a.dt_x;
+  p.c_dt = a.dt_y;
+  p.sum_dt = dt_sum;
+  if (a.res) {
+    p.A2 = (const float*)a.res;
+    p.ldsrc2 = a.ld_res;
+    p.pro_scale2 = a.res_scale;
+    p.pro_shift2 = a.res_shift;
+    p.sum_out = (float*)a.sum_out;
+    p.ld_sum = a.ld_sum;
+    p.a2_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, a.ld_res, d->in_c, dt_size(a.dt_x));
+    p.sum_bytes = a.sum_out ? extent_bytes((long)d->batch * d->in_h * d->in_w, a.ld_sum, d->in_c, dt_size(dt_sum)) : 0;
   }
-  p.b_bytes = extent_bytes((long)p.K, d->out_c, d->out_c, dt_size(ty.w));
-  p.b_dt = ty.w;
-  if (rz.bn) {
-    const dj_bn_train& b = *rz.bn;
+  p.b_bytes = extent_bytes((long)p.K, d->out_c, d->out_c, dt_size(a.dt_w));
+  p.b_dt = a.dt_w;
+  if (a.bn) {
+    const dj_bn_train& b = *a.bn;
     DJ_CHECK_ARG(b.acc && b.ticket && b.gamma && b.beta && b.scale && b.shift && b.save_mean && b.save_invstd,
                  "conv fwd (BN): null pointer in dj_bn_train");
     DJ_CHECK_ARG((b.moving_mean == nullptr) == (b.moving_var == nullptr), "conv fwd (BN): moving stats come together");
-    DJ_CHECK_ARG(stats == nullptr && !relu, "conv fwd (BN): no partial statistics / fused ReLU together with the fused finalize");
+    DJ_CHECK_ARG(a.stats == nullptr && !relu, "conv fwd (BN): no partial statistics / fused ReLU together with the fused finalize");
     p.bn_acc = b.acc;
     // one copy of the accumulators per 8192 GEMM rows: the big-M layers are the ones whose hundreds of workgroups
     // would otherwise queue on the same 2*N addresses
@@ -404,20 +428,17 @@ static int conv_fwd_impl(const dj_conv2d_desc* d, const float* x, const float* w
   }
   // statistics come out of the GEMM epilogue (one K range per tile) -- or, for a caller that allows it and supplies a
   // workspace, out of the slab reduction of a split launch (tuned like a launch without statistics)
-  const bool wants_stats = (stats != nullptr || rz.bn != nullptr) && !stats_may_split;
+  const bool wants_stats = (a.stats != nullptr || a.bn != nullptr) && !stats_may_split;
   int splits = 1;
   int cfg = choose_cfg(p.M, p.N, p.K, !wants_stats, &splits);
   tune_lookup(wants_stats ? 4 : 0, d, &cfg, &splits);
   if (wants_stats) splits = 1;
-  if (ty.y != DJ_F32) splits = 1;   // a 16-bit result is written by one K range (no slabs, no atomics)
-  p.kchunk = dj_cdiv(dj_cdiv(p.K, splits), DJ_BK) * DJ_BK;
-  splits = dj_cdiv(p.K, p.kchunk);
+  if (a.dt_y != DJ_F32) splits = 1;   // a 16-bit result is written by one K range (no slabs, no atomics)
+  splits = split_k(p.K, splits, &p.kchunk);
   // split-K through slabs in the caller's workspace + a fixed-order reduction (deterministic), when they fit
-  bool slabs = splits > 1 && ws != nullptr && !rz.bn && (long)splits * p.M * p.N <= ws_floats && aligned16(ws);
-  if (splits > 1 && !slabs && stats_may_split) {   // statistics cannot come from atomics: one K range after all
-    splits = 1;
-    p.kchunk = dj_cdiv(p.K, DJ_BK) * DJ_BK;
-  }
+  bool slabs = splits > 1 && ws != nullptr && !a.bn && (long)splits * p.M * p.N <= a.workspace_floats && aligned16(ws);
+  if (splits > 1 && !slabs && stats_may_split)   // statistics cannot come from atomics: one K range after all
+    splits = split_k(p.K, 1, &p.kchunk);
   if (slabs) {
     p.C = ws;
     p.ldc = p.N;
@@ -428,22 +449,17 @@ static int conv_fwd_impl(const dj_conv2d_desc* d, const float* x, const float* w
   } else if (splits > 1) {
     p.atomic = 1;
     p.relu = 0;
-    if (!y_zeroed) {
-      hipError_t e = hipMemset2DAsync(y, (size_t)d->ld_y * 4, 0, (size_t)d->out_c * 4, (size_t)p.M, s);
-      if (e != hipSuccess) {
-        dj_set_error("conv fwd: memset: %s", hipGetErrorString(e));
-        return DJ_ERR_HIP;
-      }
-    }
+    if (!y_zeroed)
+      if (int rc = clear_rows(y, p.M, d->out_c, d->ld_y, 4, s, "conv fwd")) return rc;
   }
-  if (rz.res) {
+  if (a.res) {
     DJ_CHECK_ARG(dj_fast_mode_fwd(p) == 3, "conv fwd (residual add): the branch-free kernel's preconditions do not hold "
                                            "(channels %% 32, 16-byte aligned tensors)");
   }
   DJ_CHECK_ARG(!io16 || dj_fast_mode_fwd(p) != 0, "conv fwd: 16-bit tensors need the branch-free kernel's preconditions "
                                                   "(in_c %% 32 == 0, out_c %% 4 == 0, 16-byte aligned tensors)");
   if (int rc = dj_launch_cfg<0, 0>(cfg, p, splits, s)) return rc;
-  if (slabs) return launch_splitk_reduce(ws, splits, p.slab_stride, p.M, p.N, bias, relu, y, d->ld_y, stats, s);
+  if (slabs) return launch_splitk_reduce(ws, splits, p.slab_stride, p.M, p.N, a.bias, relu, y, d->ld_y, a.stats, s);
   if (splits > 1 && relu) {
     long total = (long)p.M * p.N;
     int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
@@ -453,191 +469,70 @@ static int conv_fwd_impl(const dj_conv2d_desc* d, const float* x, const float* w
   return DJ_OK;
 }
 
-extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                                  float* y, const float* pro_scale, const float* pro_shift, int pro_relu, int relu,
-                                  float* stats, void* stream) {
-  return conv_fwd_impl(d, x, w, bias, y, pro_scale, pro_shift, pro_relu, relu, stats, FwdResidual(), stream);
-}
-
-// As dj_conv2d_nhwc_fwd, with a caller-owned workspace of `workspace_floats` floats (dj_conv2d_fwd_workspace_floats): a
-// split-K launch then writes its partial tiles there and a fixed-order reduction produces y -- bit-reproducible, where
-// the version without workspace accumulates with fp32 atomics in arrival order.  With DJ_CONV_STATS_MAY_SPLIT in `relu`
-// a launch with `stats` may be split too (the reduction takes the statistics).
-extern "C" int dj_conv2d_nhwc_fwd_ws(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                                     float* y, const float* pro_scale, const float* pro_shift, int pro_relu, int relu,
-                                     float* stats, float* workspace, long workspace_floats, void* stream) {
-  DJ_CHECK_ARG(workspace_floats >= 0 && (workspace != nullptr || workspace_floats == 0), "conv fwd: bad workspace");
-  return conv_fwd_impl(d, x, w, bias, y, pro_scale, pro_shift, pro_relu, relu, stats, FwdResidual(), stream, workspace,
-                       workspace_floats);
-}
-
-// Floats of workspace with which dj_conv2d_nhwc_fwd_ws runs this geometry without atomics under the CURRENT tuning
+// Floats of workspace with which dj_conv2d_nhwc_fwd runs this geometry without atomics under the CURRENT tuning
 // choice (0: the launch is not split).  may_split_stats: as the flag of the same name.
 extern "C" long dj_conv2d_fwd_workspace_floats(const dj_conv2d_desc* d, int may_split_stats) {
   if (check_desc(d)) return -1;
   const int M = d->batch * d->out_h * d->out_w, N = d->out_c, K = d->kernel_h * d->kernel_w * d->in_c;
-  int splits = 1;
+  int splits = 1, kchunk;
   int cfg = choose_cfg(M, N, K, true, &splits);
   tune_lookup(0, d, &cfg, &splits);
   (void)may_split_stats;
-  const int kchunk = dj_cdiv(dj_cdiv(K, splits), DJ_BK) * DJ_BK;
-  splits = dj_cdiv(K, kchunk);
+  splits = split_k(K, splits, &kchunk);
   return splits > 1 ? (long)splits * M * N : 0;
 }
-
-// Forward conv whose only consumer is a training-mode BatchNormalization: that layer's statistics, scale/shift and
-// moving averages are produced by the same launch (res == NULL: plain input; else the residual-add prologue above).
-extern "C" int dj_conv2d_nhwc_fwd_bn(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias, float* y,
-                                     const float* pro_scale, const float* pro_shift, int pro_relu, const float* res,
-                                     int ld_res, const float* res_scale, const float* res_shift, float* sum_out,
-                                     int ld_sum, const dj_bn_train* bn, void* stream) {
-  DJ_CHECK_ARG(bn != nullptr, "conv fwd (BN): dj_bn_train is required");
-  FwdResidual rz;
-  rz.bn = bn;
-  if (res) {
-    DJ_CHECK_ARG(d && dj_conv2d_fwd_addrelu_supported(d), "conv fwd (BN, residual add): needs a 1x1 stride-1 unpadded conv "
-                                                           "with in_c %% 32 == 0");
-    DJ_CHECK_ARG(pro_scale && pro_shift, "conv fwd (BN, residual add): pro_scale and pro_shift are required");
-    DJ_CHECK_ARG((res_scale == nullptr) == (res_shift == nullptr), "conv fwd (BN, residual add): res_scale/res_shift");
-    DJ_CHECK_ARG(ld_res >= d->in_c && ld_res % 4 == 0 && (!sum_out || (ld_sum >= d->in_c && ld_sum % 4 == 0)),
-                 "conv fwd (BN, residual add): bad ld_res / ld_sum");
-    DJ_CHECK_ARG(aligned16(res) && aligned16(sum_out) && aligned16(res_scale) && aligned16(res_shift),
-                 "conv fwd (BN, residual add): tensors must be 16-byte aligned");
-    rz.res = res;
-    rz.ld_res = ld_res;
-    rz.res_scale = res_scale;
-    rz.res_shift = res_shift;
-    rz.sum_out = sum_out;
-    rz.ld_sum = ld_sum;
-    pro_relu = 1;
-  }
-  return conv_fwd_impl(d, x, w, bias, y, pro_scale, pro_shift, pro_relu, 0, nullptr, rz, stream);
-}
-
-extern "C" int dj_conv2d_fwd_addrelu_supported(const dj_conv2d_desc* d) {
-  if (check_desc(d)) return 0;
-  return d->kernel_h == 1 && d->kernel_w == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_top == 0 &&
-         d->pad_left == 0 && d->in_h == d->out_h && d->in_w == d->out_w && d->in_c % 32 == 0 && d->ld_x % 4 == 0 &&
-         d->out_c % 4 == 0;
-}
-
-static int conv_fwd_addrelu_impl(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                                 float* y, const float* pro_scale, const float* pro_shift, const float* res,
-                                 int ld_res, const float* res_scale, const float* res_shift, float* sum_out,
-                                 int ld_sum, int relu, float* stats, float* ws, long ws_floats, void* stream,
-                                 const FwdTypes& ty = FwdTypes()) {
-  DJ_CHECK_ARG(d && dj_conv2d_fwd_addrelu_supported(d), "conv fwd (residual add): needs a 1x1 stride-1 unpadded conv with "
-                                                         "in_c %% 32 == 0");
-  DJ_CHECK_ARG(res && pro_scale && pro_shift, "conv fwd (residual add): res, pro_scale and pro_shift are required");
-  DJ_CHECK_ARG((res_scale == nullptr) == (res_shift == nullptr), "conv fwd (residual add): res_scale/res_shift come together");
-  DJ_CHECK_ARG(ld_res >= d->in_c && ld_res % 4 == 0 && (!sum_out || (ld_sum >= d->in_c && ld_sum % 4 == 0)),
-               "conv fwd (residual add): bad ld_res / ld_sum");
-  DJ_CHECK_ARG(aligned16(res) && aligned16(sum_out) && aligned16(res_scale) && aligned16(res_shift),
-               "conv fwd (residual add): tensors must be 16-byte aligned");
-  FwdResidual rz;
-  rz.res = res;
-  rz.ld_res = ld_res;
-  rz.res_scale = res_scale;
-  rz.res_shift = res_shift;
-  rz.sum_out = sum_out;
-  rz.ld_sum = ld_sum;
-  return conv_fwd_impl(d, x, w, bias, y, pro_scale, pro_shift, 1, relu, stats, rz, stream, ws, ws_floats, ty);
-}
-
-// Forward convolution over tensors that carry their storage type (include/dj_hip.h): the superset of dj_conv2d_nhwc_fwd_ws
-// (res == NULL) and dj_conv2d_nhwc_fwd_addrelu_ws.
-extern "C" int dj_conv2d_nhwc_fwd_t(const dj_conv2d_desc* d, const void* x, int dt_x, const void* w, int dt_w, const float* bias,
-                                    void* y, int dt_y, const float* pro_scale, const float* pro_shift, int pro_relu, int relu,
-                                    float* stats, const void* res, int ld_res, const float* res_scale,
-                                    const float* res_shift, void* sum_out, int ld_sum, int dt_sum, float* workspace,
-                                    long workspace_floats, void* stream) {
-  DJ_CHECK_ARG(dt_ok(dt_x) && dt_ok(dt_w) && dt_ok(dt_y) && dt_ok(dt_sum), "conv fwd: unknown storage type");
-  DJ_CHECK_ARG(workspace_floats >= 0 && (workspace != nullptr || workspace_floats == 0), "conv fwd: bad workspace");
-  FwdTypes ty;
-  ty.x = dt_x;
-  ty.w = dt_w;
-  ty.y = dt_y;
-  ty.sum = sum_out ? dt_sum : DJ_F32;
-  if (res)
-    return conv_fwd_addrelu_impl(d, (const float*)x, (const float*)w, bias, (float*)y, pro_scale, pro_shift, (const float*)res, ld_res,
-                                 res_scale, res_shift, (float*)sum_out, ld_sum, relu, stats, workspace, workspace_floats,
-                                 stream, ty);
-  DJ_CHECK_ARG(!sum_out, "conv fwd: sum_out without res");
-  return conv_fwd_impl(d, (const float*)x, (const float*)w, bias, (float*)y, pro_scale, pro_shift, pro_relu, relu, stats,
-                       FwdResidual(), stream, workspace, workspace_floats, ty);
-}
-
-extern "C" int dj_conv2d_nhwc_fwd_addrelu(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                                          float* y, const float* pro_scale, const float* pro_shift, const float* res,
-                                          int ld_res, const float* res_scale, const float* res_shift, float* sum_out,
-                                          int ld_sum, int relu, float* stats, void* stream) {
-  return conv_fwd_addrelu_impl(d, x, w, bias, y, pro_scale, pro_shift, res, ld_res, res_scale, res_shift, sum_out, ld_sum,
-                               relu, stats, nullptr, 0, stream);
-}
-
-// dj_conv2d_nhwc_fwd_addrelu with the split-K workspace of dj_conv2d_nhwc_fwd_ws (same rules, same size query)
-extern "C" int dj_conv2d_nhwc_fwd_addrelu_ws(const dj_conv2d_desc* d, const float* x, const float* w, const float* bias,
-                                             float* y, const float* pro_scale, const float* pro_shift, const float* res,
-                                             int ld_res, const float* res_scale, const float* res_shift, float* sum_out,
-                                             int ld_sum, int relu, float* stats, float* workspace, long workspace_floats,
-                                             void* stream) {
-  DJ_CHECK_ARG(workspace_floats >= 0 && (workspace != nullptr || workspace_floats == 0), "conv fwd (residual add): bad workspace");
-  return conv_fwd_addrelu_impl(d, x, w, bias, y, pro_scale, pro_shift, res, ld_res, res_scale, res_shift, sum_out, ld_sum,
-                               relu, stats, workspace, workspace_floats, stream);
-}
-
-struct DgradBnBwd {   // dj_conv2d_nhwc_dgrad_bnbwd: see include/dj_hip.h
-  const float* z;
-  int dt_z;
-  int ld_z;
-  const float* mean;
-  const float* invstd;
-  const float* scale;
-  const float* shift;
-  float* partial;
-};
-
-struct DgradReluMask {   // dj_conv2d_nhwc_dgrad_relumask: see include/dj_hip.h
-  const float* x;
-  int ld;
-};
 
 static inline bool dgrad_is_strided_1x1(const dj_conv2d_desc* d) {
   return d->kernel_h == 1 && d->kernel_w == 1 && d->pad_top == 0 && d->pad_left == 0 && (d->stride_h > 1 || d->stride_w > 1) &&
          d->stride_h == d->stride_w;
 }
 
-static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias, float* dx, int beta,
-                           const DgradBnBwd* bnb, void* stream, int dt_dy = DJ_F32, int dt_dx = DJ_F32, int dt_w = DJ_F32,
-                           const DgradReluMask* rm = nullptr) {
+extern "C" int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const dj_conv_dgrad_args* args, void* stream) {
+  DJ_CHECK_ARG(args != nullptr, "conv dgrad: null argument struct");
+  const dj_conv_dgrad_args& a = *args;
+  DJ_CHECK_ARG(dt_ok(a.dt_dy) && dt_ok(a.dt_w) && dt_ok(a.dt_dx) && dt_ok(a.dt_z), "conv dgrad: unknown storage type");
+  // the BatchNormalization backward statistics are asked for by `partial`; z alone is no plain input gradient either
+  const bool bnb = a.partial != nullptr || a.z != nullptr;
+  if (bnb) {
+    DJ_CHECK_ARG(a.z && a.mean && a.invstd && a.partial, "conv dgrad + BN backward statistics: null tensor");
+    DJ_CHECK_ARG((a.scale == nullptr) == (a.shift == nullptr), "conv dgrad + BN backward statistics: scale/shift must come together");
+    // one K range per tile, no accumulation: the accumulator of a tile IS the gradient the statistics are taken of
+    DJ_CHECK_ARG(d && a.ld_z >= d->in_c && !a.bias && !(a.flags & 1), "conv dgrad + BN backward statistics: ld_z < in_c, or a bias / "
+                                                                      "an accumulating launch");
+  }
+  if (a.mask_x) {
+    DJ_CHECK_ARG(d && a.ld_mask >= d->in_c, "conv dgrad + ReLU mask: ld_mask < in_c");
+    DJ_CHECK_ARG((long)d->batch * d->in_h * d->in_w * (long)a.ld_mask < (1L << 31), "conv dgrad + ReLU mask: mask exceeds 2^31 elements");
+  }
   if (int rc = check_desc(d)) return rc;
-  DJ_CHECK_ARG(dy && w && dx, "conv dgrad: null tensor");
-  const bool io16 = dt_dy != DJ_F32 || dt_dx != DJ_F32 || dt_w != DJ_F32 || (bnb && bnb->dt_z != DJ_F32);
-  DJ_CHECK_ARG((dt_dy == DJ_F32 || dt_dy == DJ_BF16) && (dt_w == DJ_F32 || dt_w == DJ_BF16) &&
-                   (!bnb || bnb->dt_z == DJ_F32 || bnb->dt_z == DJ_F16),
+  DJ_CHECK_ARG(a.dy && a.w && a.dx, "conv dgrad: null tensor");
+  const int dt_z = bnb ? a.dt_z : DJ_F32;
+  const bool io16 = a.dt_dy != DJ_F32 || a.dt_dx != DJ_F32 || a.dt_w != DJ_F32 || dt_z != DJ_F32;
+  DJ_CHECK_ARG((a.dt_dy == DJ_F32 || a.dt_dy == DJ_BF16) && (a.dt_w == DJ_F32 || a.dt_w == DJ_BF16) &&
+                   (dt_z == DJ_F32 || dt_z == DJ_F16),
                "conv dgrad: gradients and the weight shadow are held as fp32 or bf16, the BatchNormalization input as fp32 or fp16");
   DJ_CHECK_ARG(!io16 || dj_compute_mode() == 1, "conv dgrad: 16-bit tensors need arithmetic mode 1 (float16)");
-  const bool one_k_range = (beta & DJ_DGRAD_NO_SPLIT) != 0;   // no split-K: no arrival-order arithmetic
-  beta &= 1;
+  const bool one_k_range = bnb || (a.flags & DJ_DGRAD_NO_SPLIT) != 0;   // no split-K: no arrival-order arithmetic
+  const int beta = a.flags & 1;
   hipStream_t s = (hipStream_t)stream;
   DjIgemmParams p;
   memset(&p, 0, sizeof(p));
   if (bnb) {
-    p.bnb_z = bnb->z;
-    p.bnb_ldz = bnb->ld_z;
-    p.bnb_zbytes = extent_bytes((long)d->batch * d->in_h * d->in_w, bnb->ld_z, d->in_c, dt_size(bnb->dt_z));
-    p.bnb_zdt = bnb->dt_z;
+    p.bnb_z = (const float*)a.z;
+    p.bnb_ldz = a.ld_z;
+    p.bnb_zbytes = extent_bytes((long)d->batch * d->in_h * d->in_w, a.ld_z, d->in_c, dt_size(dt_z));
+    p.bnb_zdt = dt_z;
     DJ_CHECK_ARG(p.bnb_zbytes > 0, "conv dgrad + BN backward statistics: z of 2 GiB or more");
-    p.bnb_mean = bnb->mean;
-    p.bnb_invstd = bnb->invstd;
-    p.bnb_scale = bnb->scale;
-    p.bnb_shift = bnb->shift;
-    p.stats = bnb->partial;
+    p.bnb_mean = a.mean;
+    p.bnb_invstd = a.invstd;
+    p.bnb_scale = a.scale;
+    p.bnb_shift = a.shift;
+    p.stats = a.partial;
   }
-  p.A = dy;
-  p.B = w;
-  p.C = dx;
-  p.bias = bias;
+  p.A = (const float*)a.dy;
+  p.B = (const float*)a.w;
+  p.C = (float*)a.dx;
+  p.bias = a.bias;
   p.N = d->in_c;
   p.srcC = d->out_c;
   p.ldsrc = d->ld_y;
@@ -645,25 +540,24 @@ static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float
   p.bTapStride = (long)d->in_c * d->out_c;
   p.ldc = d->ld_x;
   p.beta = beta;
-  p.vecA = (d->out_c % 4 == 0) && (d->ld_y % 4 == 0) && aligned_dt(dy, dt_dy);
-  p.vecB = (d->out_c % 4 == 0) && aligned_dt(w, dt_w);
-  p.a_bytes = extent_bytes((long)d->batch * d->out_h * d->out_w, d->ld_y, d->out_c, dt_size(dt_dy));
-  p.b_bytes = extent_bytes((long)d->kernel_h * d->kernel_w * d->in_c, d->out_c, d->out_c, dt_size(dt_w));
-  p.b_dt = dt_w;
-  p.a_dt = dt_dy;
-  p.c_dt = dt_dx;
-  const int es_dx = dt_size(dt_dx);
+  p.vecA = (d->out_c % 4 == 0) && (d->ld_y % 4 == 0) && aligned_dt(a.dy, a.dt_dy);
+  p.vecB = (d->out_c % 4 == 0) && aligned_dt(a.w, a.dt_w);
+  p.a_bytes = extent_bytes((long)d->batch * d->out_h * d->out_w, d->ld_y, d->out_c, dt_size(a.dt_dy));
+  p.b_bytes = extent_bytes((long)d->kernel_h * d->kernel_w * d->in_c, d->out_c, d->out_c, dt_size(a.dt_w));
+  p.b_dt = a.dt_w;
+  p.a_dt = a.dt_dy;
+  p.c_dt = a.dt_dx;
   const long in_pixels = (long)d->batch * d->in_h * d->in_w;
-  bool strided_1x1 = dgrad_is_strided_1x1(d) && bias == nullptr;
+  bool strided_1x1 = dgrad_is_strided_1x1(d) && a.bias == nullptr;
   int splits = 1;
   DJ_CHECK_ARG(!(bnb && strided_1x1), "conv dgrad + BN backward statistics: not for strided 1x1 convolutions");
-  if (rm) {
+  if (a.mask_x) {
     DJ_CHECK_ARG(!bnb && !io16, "conv dgrad + ReLU mask: fp32 tensors, no BN backward statistics");
     DJ_CHECK_ARG(!dgrad_is_strided_1x1(d), "conv dgrad + ReLU mask: not for strided 1x1 convolutions (their dx is scattered)");
     const int mode = dj_compute_mode();
     DJ_CHECK_ARG(mode != 1 && mode != 2, "conv dgrad + ReLU mask: not in the 16-bit arithmetic modes");
-    p.mask_x = rm->x;
-    p.ld_mask = rm->ld;
+    p.mask_x = a.mask_x;
+    p.ld_mask = a.ld_mask;
   }
   if (strided_1x1) {
     // compact GEMM over the output grid, rows scattered to the strided input pixels
@@ -683,16 +577,11 @@ static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float
     p.cH = d->in_h;
     p.cW = d->in_w;
     p.cS = d->stride_h;
-    if (!beta) {
-      hipError_t e = hipMemset2DAsync(dx, (size_t)d->ld_x * es_dx, 0, (size_t)d->in_c * es_dx, (size_t)in_pixels, s);
-      if (e != hipSuccess) {
-        dj_set_error("conv dgrad: memset: %s", hipGetErrorString(e));
-        return DJ_ERR_HIP;
-      }
-    }
+    if (!beta)
+      if (int rc = clear_rows(a.dx, in_pixels, d->in_c, d->ld_x, dt_size(a.dt_dx), s, "conv dgrad")) return rc;
     int cfg = choose_cfg(p.M, p.N, p.K, false, &splits);
     tune_lookup(1, d, &cfg, &splits);
-    p.kchunk = dj_cdiv(p.K, DJ_BK) * DJ_BK;
+    split_k(p.K, 1, &p.kchunk);
     DJ_CHECK_ARG(!io16 || (fast_mode<0, 1>(p)) != 0, "conv dgrad (strided 1x1): 16-bit tensors need the branch-free kernel's "
                                                    "preconditions (channels %% 32, 16-byte aligned tensors)");
     return dj_launch_cfg<0, 1>(cfg, p, 1, s);
@@ -710,45 +599,23 @@ static int conv_dgrad_impl(const dj_conv2d_desc* d, const float* dy, const float
   // entry of its own (direction 9), falling back to the plain input gradient's tile variant
   bool tuned1 = false;
   if (!(bnb && tune_lookup(9, d, &cfg, &splits))) tuned1 = tune_lookup(1, d, &cfg, &splits);
-  if (rm) {
+  if (a.mask_x) {
     // the masked accumulate completes the value in registers: one K range.  A registered split factor is a measured
     // choice this launch cannot honour -- an error; the launcher's untuned guess is simply not split
     DJ_CHECK_ARG(!(tuned1 && splits > 1), "conv dgrad + ReLU mask: the tuning entry of this geometry splits the reduction");
     splits = 1;
   }
-  if (one_k_range || dt_dx != DJ_F32) splits = 1;   // (a 16-bit result is written by one K range: no atomics)
-  p.kchunk = dj_cdiv(dj_cdiv(p.K, splits), DJ_BK) * DJ_BK;
-  splits = dj_cdiv(p.K, p.kchunk);
+  if (one_k_range || a.dt_dx != DJ_F32) splits = 1;   // (a 16-bit result is written by one K range: no atomics)
+  splits = split_k(p.K, splits, &p.kchunk);
   DJ_CHECK_ARG(!io16 || (fast_mode<1, 1>(p)) != 0, "conv dgrad: 16-bit tensors need the branch-free kernel's preconditions "
                                                  "(stride 1, channels %% 32, 16-byte aligned tensors)");
   if (splits > 1) {
     p.atomic = 1;
-    if (!beta) {
-      hipError_t e = hipMemset2DAsync(dx, (size_t)d->ld_x * 4, 0, (size_t)d->in_c * 4, (size_t)in_pixels, s);
-      if (e != hipSuccess) {
-        dj_set_error("conv dgrad: memset: %s", hipGetErrorString(e));
-        return DJ_ERR_HIP;
-      }
-    }
+    if (!beta)
+      if (int rc = clear_rows(a.dx, in_pixels, d->in_c, d->ld_x, 4, s, "conv dgrad")) return rc;
     p.beta = 0;
   }
   return dj_launch_cfg<1, 1>(cfg, p, splits, s);
-}
-
-extern "C" int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias,
-                                    float* dx, int beta, void* stream) {
-  return conv_dgrad_impl(d, dy, w, bias, dx, beta, nullptr, stream);
-}
-
-extern "C" int dj_conv2d_nhwc_dgrad_bnbwd(const dj_conv2d_desc* d, const float* dy, const float* w, float* dx, const float* z,
-                                          int ld_z, const float* mean, const float* invstd, const float* scale,
-                                          const float* shift, float* partial, void* stream) {
-  DJ_CHECK_ARG(z && mean && invstd && partial, "conv dgrad + BN backward statistics: null tensor");
-  DJ_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv dgrad + BN backward statistics: scale/shift must come together");
-  DJ_CHECK_ARG(d && ld_z >= d->in_c, "conv dgrad + BN backward statistics: ld_z < in_c");
-  DgradBnBwd b{z, DJ_F32, ld_z, mean, invstd, scale, shift, partial};
-  // one K range per tile, no accumulation: the accumulator of a tile IS the gradient the statistics are taken of
-  return conv_dgrad_impl(d, dy, w, nullptr, dx, DJ_DGRAD_NO_SPLIT, &b, stream);
 }
 
 extern "C" int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d) {
@@ -760,51 +627,45 @@ extern "C" int dj_conv2d_dgrad_relumask_supported(const dj_conv2d_desc* d) {
   return 1;
 }
 
-extern "C" int dj_conv2d_nhwc_dgrad_relumask(const dj_conv2d_desc* d, const float* dy, const float* w, const float* bias,
-                                             float* dx, int beta, const float* mask_x, int ld_mask, void* stream) {
-  DJ_CHECK_ARG(mask_x != nullptr, "conv dgrad + ReLU mask: null mask tensor");
-  DJ_CHECK_ARG(d && ld_mask >= d->in_c, "conv dgrad + ReLU mask: ld_mask < in_c");
-  DJ_CHECK_ARG(d && (long)d->batch * d->in_h * d->in_w * (long)ld_mask < (1L << 31), "conv dgrad + ReLU mask: mask exceeds 2^31 elements");
-  DgradReluMask m{mask_x, ld_mask};
-  return conv_dgrad_impl(d, dy, w, bias, dx, beta & 1, nullptr, stream, DJ_F32, DJ_F32, DJ_F32, &m);
+// The weight gradient's untuned choice: tile by the (taps*Cin) x Cout extent only -- the pixel reduction is split over
+// blockIdx.y to fill the chip
+static int choose_cfg_wgrad(long M, long N, long K, int* splits_out) {
+  int cfg;
+  if (N > 96 && (long)dj_cdiv(N, 128) * 128 <= (long)dj_cdiv(N, 64) * 64)
+    cfg = (M >= 128) ? CFG_128x128 : CFG_64x64;
+  else if (N > 32)
+    cfg = (M >= 128) ? CFG_128x64 : CFG_64x64;
+  else
+    cfg = CFG_128x32;
+  long t = (long)dj_cdiv(M, kCfgs[cfg].bm) * dj_cdiv(N, kCfgs[cfg].bn);
+  long want = (768 + t - 1) / t;
+  long maxs = K / 128;
+  if (maxs < 1) maxs = 1;
+  *splits_out = (int)(want < maxs ? want : maxs);
+  if (*splits_out < 1) *splits_out = 1;
+  return cfg;
 }
 
-// Input gradient over tensors that carry their storage type: the superset of dj_conv2d_nhwc_dgrad (z == NULL) and
-// dj_conv2d_nhwc_dgrad_bnbwd.
-extern "C" int dj_conv2d_nhwc_dgrad_t(const dj_conv2d_desc* d, const void* dy, int dt_dy, const void* w, int dt_w,
-                                      const float* bias, void* dx, int dt_dx, int beta, const void* z, int ld_z, int dt_z, const float* mean,
-                                      const float* invstd, const float* scale, const float* shift, float* partial,
-                                      void* stream) {
-  DJ_CHECK_ARG(dt_ok(dt_dy) && dt_ok(dt_w) && dt_ok(dt_dx) && dt_ok(dt_z), "conv dgrad: unknown storage type");
-  if (!z)
-    return conv_dgrad_impl(d, (const float*)dy, (const float*)w, bias, (float*)dx, beta, nullptr, stream, dt_dy, dt_dx, dt_w);
-  DJ_CHECK_ARG(mean && invstd && partial, "conv dgrad + BN backward statistics: null tensor");
-  DJ_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv dgrad + BN backward statistics: scale/shift must come together");
-  DJ_CHECK_ARG(d && ld_z >= d->in_c && !bias && !(beta & 1), "conv dgrad + BN backward statistics: ld_z < in_c, or a bias / "
-                                                              "an accumulating launch");
-  DgradBnBwd b{(const float*)z, dt_z, ld_z, mean, invstd, scale, shift, partial};
-  return conv_dgrad_impl(d, (const float*)dy, (const float*)w, nullptr, (float*)dx, DJ_DGRAD_NO_SPLIT, &b, stream, dt_dy, dt_dx,
-                         dt_w);
-}
-
-static int conv_wgrad_impl(const dj_conv2d_desc* d, const float* x, const float* dy, float* dw, const float* pro_scale,
-                           const float* pro_shift, int pro_relu, int dw_zeroed, void* stream, int dt_x, int dt_dy) {
+extern "C" int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const dj_conv_wgrad_args* args, void* stream) {
+  DJ_CHECK_ARG(args != nullptr, "conv wgrad: null argument struct");
+  const dj_conv_wgrad_args& a = *args;
+  DJ_CHECK_ARG(dt_ok(a.dt_x) && dt_ok(a.dt_dy), "conv wgrad: unknown storage type");
   if (int rc = check_desc(d)) return rc;
-  DJ_CHECK_ARG(x && dy && dw, "conv wgrad: null tensor");
-  const bool io16 = dt_x != DJ_F32 || dt_dy != DJ_F32;
-  DJ_CHECK_ARG((dt_x == DJ_F32 || dt_x == DJ_F16) && (dt_dy == DJ_F32 || dt_dy == DJ_BF16),
+  DJ_CHECK_ARG(a.x && a.dy && a.dw, "conv wgrad: null tensor");
+  const bool io16 = a.dt_x != DJ_F32 || a.dt_dy != DJ_F32;
+  DJ_CHECK_ARG((a.dt_x == DJ_F32 || a.dt_x == DJ_F16) && (a.dt_dy == DJ_F32 || a.dt_dy == DJ_BF16),
                "conv wgrad: activations are held as fp32 or fp16, gradients as fp32 or bf16");
   DJ_CHECK_ARG(!io16 || dj_compute_mode() == 1, "conv wgrad: 16-bit tensors need arithmetic mode 1 (float16)");
-  DJ_CHECK_ARG((pro_scale == nullptr) == (pro_shift == nullptr), "conv wgrad: pro_scale/pro_shift must come together");
+  DJ_CHECK_ARG((a.pro_scale == nullptr) == (a.pro_shift == nullptr), "conv wgrad: pro_scale/pro_shift must come together");
   hipStream_t s = (hipStream_t)stream;
   DjIgemmParams p;
   memset(&p, 0, sizeof(p));
-  p.A = x;
-  p.B = dy;
-  p.C = dw;
-  p.pro_scale = pro_scale;
-  p.pro_shift = pro_shift;
-  p.pro_relu = pro_relu;
+  p.A = (const float*)a.x;
+  p.B = (const float*)a.dy;
+  p.C = a.dw;
+  p.pro_scale = a.pro_scale;
+  p.pro_shift = a.pro_shift;
+  p.pro_relu = a.pro_relu;
   p.M = d->kernel_h * d->kernel_w * d->in_c;
   p.N = d->out_c;
   p.K = d->batch * d->out_h * d->out_w;
@@ -818,59 +679,25 @@ static int conv_wgrad_impl(const dj_conv2d_desc* d, const float* x, const float*
   p.ldb = d->ld_y;
   p.ldc = d->out_c;
   p.cmap = 0;
-  p.vecA = (d->in_c % 4 == 0) && (d->ld_x % 4 == 0) && aligned_dt(x, dt_x) &&
-           (!pro_scale || (aligned16(pro_scale) && aligned16(pro_shift)));
-  p.vecB = (d->out_c % 4 == 0) && (d->ld_y % 4 == 0) && aligned_dt(dy, dt_dy);
-  p.a_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, d->ld_x, d->in_c, dt_size(dt_x));
-  p.b_bytes = extent_bytes((long)d->batch * d->out_h * d->out_w, d->ld_y, d->out_c, dt_size(dt_dy));
-  p.a_dt = dt_x;
-  p.b_dt = dt_dy;
-  // tile by the (taps*Cin) x Cout extent only -- the pixel reduction is split over blockIdx.y to fill the chip
+  p.vecA = (d->in_c % 4 == 0) && (d->ld_x % 4 == 0) && aligned_dt(a.x, a.dt_x) &&
+           (!a.pro_scale || (aligned16(a.pro_scale) && aligned16(a.pro_shift)));
+  p.vecB = (d->out_c % 4 == 0) && (d->ld_y % 4 == 0) && aligned_dt(a.dy, a.dt_dy);
+  p.a_bytes = extent_bytes((long)d->batch * d->in_h * d->in_w, d->ld_x, d->in_c, dt_size(a.dt_x));
+  p.b_bytes = extent_bytes((long)d->batch * d->out_h * d->out_w, d->ld_y, d->out_c, dt_size(a.dt_dy));
+  p.a_dt = a.dt_x;
+  p.b_dt = a.dt_dy;
   int splits = 1;
-  int cfg;
-  if (p.N > 96 && (long)dj_cdiv(p.N, 128) * 128 <= (long)dj_cdiv(p.N, 64) * 64)
-    cfg = (p.M >= 128) ? CFG_128x128 : CFG_64x64;
-  else if (p.N > 32)
-    cfg = (p.M >= 128) ? CFG_128x64 : CFG_64x64;
-  else
-    cfg = CFG_128x32;
-  long t = (long)dj_cdiv(p.M, kCfgs[cfg].bm) * dj_cdiv(p.N, kCfgs[cfg].bn);
-  long want = (768 + t - 1) / t;
-  long maxs = p.K / 128;
-  if (maxs < 1) maxs = 1;
-  splits = (int)(want < maxs ? want : maxs);
-  if (splits < 1) splits = 1;
+  int cfg = choose_cfg_wgrad(p.M, p.N, p.K, &splits);
   tune_lookup(2, d, &cfg, &splits);
-  p.kchunk = dj_cdiv(dj_cdiv(p.K, splits), DJ_BK) * DJ_BK;
-  splits = dj_cdiv(p.K, p.kchunk);
+  splits = split_k(p.K, splits, &p.kchunk);
   if (splits > 1) {
     p.atomic = 1;
-    if (!dw_zeroed) {
-      hipError_t e = hipMemsetAsync(dw, 0, (size_t)p.M * p.N * 4, s);
-      if (e != hipSuccess) {
-        dj_set_error("conv wgrad: memset: %s", hipGetErrorString(e));
-        return DJ_ERR_HIP;
-      }
-    }
+    if (!a.dw_zeroed)
+      if (int rc = memset_status(hipMemsetAsync(a.dw, 0, (size_t)p.M * p.N * 4, s), "conv wgrad")) return rc;
   }
   DJ_CHECK_ARG(!io16 || (fast_mode<2, 0>(p)) != 0, "conv wgrad: 16-bit tensors need the branch-free kernel's preconditions "
                                                  "(channels %% 4, 16-byte aligned tensors)");
   return dj_launch_cfg<2, 0>(cfg, p, splits, s);
-}
-
-extern "C" int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const float* x, const float* dy, float* dw,
-                                    const float* pro_scale, const float* pro_shift, int pro_relu, int dw_zeroed,
-                                    void* stream) {
-  return conv_wgrad_impl(d, x, dy, dw, pro_scale, pro_shift, pro_relu, dw_zeroed, stream, DJ_F32, DJ_F32);
-}
-
-// Weight gradient over tensors that carry their storage type (dw is always the fp32 gradient of the master weights).
-extern "C" int dj_conv2d_nhwc_wgrad_t(const dj_conv2d_desc* d, const void* x, int dt_x, const void* dy, int dt_dy, float* dw,
-                                      const float* pro_scale, const float* pro_shift, int pro_relu, int dw_zeroed,
-                                      void* stream) {
-  DJ_CHECK_ARG(dt_ok(dt_x) && dt_ok(dt_dy), "conv wgrad: unknown storage type");
-  return conv_wgrad_impl(d, (const float*)x, (const float*)dy, dw, pro_scale, pro_shift, pro_relu, dw_zeroed, stream, dt_x,
-                         dt_dy);
 }
 
 extern "C" int dj_conv2d_default_config(int dir, const dj_conv2d_desc* d, int* cfg, int* splits) {
@@ -878,32 +705,14 @@ extern "C" int dj_conv2d_default_config(int dir, const dj_conv2d_desc* d, int* c
   DJ_CHECK_ARG(cfg && splits, "default_config: null output");
   int base = dir & 3;
   *splits = 1;
-  if (base == 0) {
+  if (base == 0)
     *cfg = choose_cfg((long)d->batch * d->out_h * d->out_w, d->out_c, (long)d->kernel_h * d->kernel_w * d->in_c,
                       (dir & 4) == 0, splits);
-  } else if (base == 1) {
-    bool strided_1x1 = d->kernel_h == 1 && d->kernel_w == 1 && d->pad_top == 0 && d->pad_left == 0 &&
-                       (d->stride_h > 1 || d->stride_w > 1) && d->stride_h == d->stride_w;
-    if (strided_1x1)
-      *cfg = choose_cfg((long)d->batch * d->out_h * d->out_w, d->in_c, d->out_c, false, splits);
-    else
-      *cfg = choose_cfg((long)d->batch * d->in_h * d->in_w, d->in_c, (long)d->kernel_h * d->kernel_w * d->out_c, true,
-                        splits);
-  } else {
-    long M = (long)d->kernel_h * d->kernel_w * d->in_c, N = d->out_c, K = (long)d->batch * d->out_h * d->out_w;
-    int c;
-    if (N > 96 && (long)dj_cdiv(N, 128) * 128 <= (long)dj_cdiv(N, 64) * 64)
-      c = (M >= 128) ? CFG_128x128 : CFG_64x64;
-    else if (N > 32)
-      c = (M >= 128) ? CFG_128x64 : CFG_64x64;
-    else
-      c = CFG_128x32;
-    long t = (long)dj_cdiv(M, kCfgs[c].bm) * dj_cdiv(N, kCfgs[c].bn);
-    long want = (768 + t - 1) / t, maxs = K / 128;
-    if (maxs < 1) maxs = 1;
-    *cfg = c;
-    *splits = (int)(want < maxs ? want : maxs);
-    if (*splits < 1) *splits = 1;
-  }
+  else if (base == 1 && dgrad_is_strided_1x1(d))
+    *cfg = choose_cfg((long)d->batch * d->out_h * d->out_w, d->in_c, d->out_c, false, splits);
+  else if (base == 1)
+    *cfg = choose_cfg((long)d->batch * d->in_h * d->in_w, d->in_c, (long)d->kernel_h * d->kernel_w * d->out_c, true, splits);
+  else
+    *cfg = choose_cfg_wgrad((long)d->kernel_h * d->kernel_w * d->in_c, d->out_c, (long)d->batch * d->out_h * d->out_w, splits);
   return DJ_OK;
 }

@@ -438,7 +438,7 @@ class Plan(object):
     # ---- split-K workspaces of the forward convolutions ---------------------------------------------------------------
     def conv_workspace(self, desc, side=False, stats_may_split=False):
         """Holder of the workspace through which the forward convolutions issued on one stream (main / side) run their
-        split-K launches WITHOUT atomics (dj_conv2d_nhwc_fwd_ws: slabs + fixed-order reduction, bit-reproducible).
+        split-K launches WITHOUT atomics (dj_conv_fwd_args.workspace: slabs + fixed-order reduction, bit-reproducible).
         Sized for the current tuning choice of every registered geometry; `finalize_workspaces` sizes it again once the
         tuner has had its say.  Launches on one stream are serial, so one buffer per stream serves them all."""
         ws = self._workspaces.setdefault(bool(side), _Workspace(self.device))

@@ -490,7 +490,7 @@ class Conv2D(Layer):
         # evenly when its reduction is split over workgroups (400 equal tiles on 256 CUs: 144 CUs carry two, the launch
         # takes two tile times for 1.56 of work), and a split launch cannot take the BatchNormalization statistics in its
         # epilogue (every workgroup holds a partial sum).  There the statistics come from the fixed-order reduction of
-        # the split launch's slabs instead (dj_conv2d_nhwc_fwd_ws with DJ_CONV_STATS_MAY_SPLIT).
+        # the split launch's slabs instead (dj_conv_fwd_args.workspace with DJ_CONV_STATS_MAY_SPLIT).
         # Same box, deconv B=32: limit 256 -> 25.08 ms, 512..700 -> 24.94, 1500 -> 25.12.
         tile_limit = int(os.environ.get("DJ_SPLIT_SMALL_BN_TILES", "512"))
         few_tiles = (-(-(b * desc.out_h * desc.out_w) // 64)) * (-(-self.filters // 64)) < tile_limit
@@ -556,7 +556,7 @@ class Conv2D(Layer):
             dy = out.grad.buf
             if relu:
                 rows, c, ld = rows_of(dy)
-                plan.emit_bwd(launcher("dj_relu_bwd", dy, ld, y, c, dy, ld, rows, c, 0))
+                plan.emit_bwd(launcher(*Kn.relu_bwd_call(dy, ld, y, c, dy, ld, rows, c, 0)))
             if self.bias is not None and self.bias.trainable:
                 if bn_consumer:
                     # the only consumer is a training-mode BatchNormalization: it subtracts the batch mean, so
@@ -578,7 +578,7 @@ class Conv2D(Layer):
                 bnv = _bn_backward_fusable(plan, model, self, x)
                 if bnv is not None and not own_memset and x.grad is None:
                     # x = [relu](bn(z)) and this convolution is its only reader: the input-gradient GEMM takes that
-                    # BatchNormalization's backward statistics in its epilogue (dj_conv2d_nhwc_dgrad_bnbwd), the layer's
+                    # BatchNormalization's backward statistics in its epilogue (dj_conv_dgrad_args.partial), the layer's
                     # own pass over (gradient, z) -- dj_bn_bwd_reduce -- is not launched
                     dx, beta = plan.grad_of(x)
                     assert beta == 0
@@ -722,8 +722,8 @@ class Dense(Layer):
             dy2 = zv.grad.buf
             dy = dy2.view(b, 1, 1, self.units)
             if relu:
-                plan.emit_bwd(lambda: call("dj_relu_bwd", dy2, self.units, zv.buf, self.units, dy2, self.units, b,
-                                           self.units, 0))
+                plan.emit_bwd(lambda: call(*Kn.relu_bwd_call(dy2, self.units, zv.buf, self.units, dy2, self.units, b,
+                                                             self.units, 0)))
             if self.bias is not None and self.bias.trainable:
                 _bias_grad(plan, dy2, self.bias)
             if self.kernel.trainable:
@@ -959,7 +959,7 @@ class Add(Layer):
         out.add_relu_first = first      # the layer whose input gradient is the last writer of this sum's gradient
         if first is not None:
             # no launch here: `first` (the next block's 1x1 conv) computes relu(bn(a) + b) in its A-tile prologue and
-            # stores it to y (dj_conv2d_nhwc_fwd_addrelu) -- one elementwise pass and one read of y less per block
+            # stores it to y (dj_conv_fwd_args.res) -- one elementwise pass and one read of y less per block
             out.pending_add = dict(consumer=first, z=abuf, z_scale=a.scale, z_shift=a.shift, res=bbuf, res_scale=b.scale,
                                    res_shift=b.shift)
         else:
@@ -1060,12 +1060,12 @@ class Concatenate(Layer):
                 # constant input (the anchor boxes): its slice of y is written once, now (not in a structure-only
                 # lowering on the host, which launches nothing)
                 if plan.device.type == "cuda":
-                    call("dj_copy2d", src, lds, dst, total, rws, n, 0)
+                    call(*Kn.copy2d_call(src, lds, dst, total, rws, n, 0))
             else:
                 live_parts.append((src, lds, dst, total, rws, n, 0))
         if len(live_parts) == 1:
             src, lds, dst, _, rws, n, _ = live_parts[0]
-            plan.emit(lambda: call("dj_copy2d", src, lds, dst, total, rws, n, 0))
+            plan.emit(lambda: call(*Kn.copy2d_call(src, lds, dst, total, rws, n, 0)))
         elif live_parts:
             plan.emit(engine.copy2d_multi(live_parts))     # one launch for all members
         out = Value(y, needs_grad=any(v.needs_grad for v in ins), name=self.name)
@@ -1090,7 +1090,7 @@ class Concatenate(Layer):
                     parts.append((src, total, dv, n, outer, n, beta))
             if len(parts) == 1:
                 src, _, dv, ld, r, n, beta = parts[0]
-                plan.emit_bwd(lambda: call("dj_copy2d", src, total, dv, ld, r, n, beta))
+                plan.emit_bwd(lambda: call(*Kn.copy2d_call(src, total, dv, ld, r, n, beta)))
             elif parts:
                 plan.emit_bwd(engine.copy2d_multi(parts))
 

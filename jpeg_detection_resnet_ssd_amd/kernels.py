@@ -78,7 +78,7 @@ def dt_of(t):
 
 
 def any16(*tensors):
-    """True when one of the tensors is held in 16 bits: the launch then goes through a `_t` entry point."""
+    """True when one of the tensors is held in 16 bits: an elementwise launch then goes through a `_t` entry point."""
     return any(t is not None and t.dtype != torch.float32 for t in tensors)
 
 
@@ -148,30 +148,36 @@ def conv2d_stats_rows(desc):
     return check(_lib.load().dj_conv2d_fwd_stats_rows(desc), "dj_conv2d_fwd_stats_rows")
 
 
+def _weights_ok(w, d):
+    return w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
+
+
+def _fwd(d, a, x, w, bias, y, pro_scale, pro_shift, stats, workspace):
+    """Fill the fields every forward launch has and make the call."""
+    assert _weights_ok(w, d)
+    a.x, a.dt_x, a.w, a.dt_w, a.bias, a.y, a.dt_y = ptr(x), dt_of(x), ptr(w), dt_of(w), ptr(bias), ptr(y), dt_of(y)
+    a.pro_scale, a.pro_shift, a.stats = ptr(pro_scale), ptr(pro_shift), ptr(stats)
+    if workspace is not None:
+        a.workspace, a.workspace_floats = ptr(workspace), workspace.numel()
+    check(_L().dj_conv2d_nhwc_fwd(d, a, _stream()), "dj_conv2d_nhwc_fwd")
+    return y
+
+
+def _residual(a, x, res, res_scale, res_shift, sum_out):
+    assert tuple(res.shape) == tuple(x.shape) and (sum_out is None or tuple(sum_out.shape) == tuple(x.shape))
+    assert res.dtype == x.dtype, "the residual operand is read like x: same storage type"
+    a.res, a.ld_res, a.res_scale, a.res_shift = ptr(res), _pixel_ld(res), ptr(res_scale), ptr(res_shift)
+    if sum_out is not None:
+        a.sum_out, a.ld_sum, a.dt_sum = ptr(sum_out), _pixel_ld(sum_out), dt_of(sum_out)
+
+
 def conv2d_fwd(desc, x, w, bias, y, pro_scale=None, pro_shift=None, pro_relu=False, relu=False, stats=None,
                y_zeroed=False, workspace=None, stats_may_split=False):
     """`y_zeroed`: y is all zeros on entry (a split-K launch then skips its own memset).
     `workspace` (float tensor): split-K launches go through slabs + a fixed-order reduction (bit-reproducible) when it is
     large enough (conv2d_fwd_workspace_floats); `stats_may_split`: a launch with `stats` may then be split too."""
-    d = _desc_for(desc, x, y)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
-    if any16(x, y, w):
-        flags = int(bool(relu)) | (2 if y_zeroed else 0) | (4 if stats_may_split else 0)
-        check(_L().dj_conv2d_nhwc_fwd_t(d, ptr(x), dt_of(x), ptr(w), dt_of(w), ptr(bias), ptr(y), dt_of(y), ptr(pro_scale),
-                                               ptr(pro_shift), int(pro_relu), flags, ptr(stats), None, 0, None, None, None, 0, 0,
-                                               ptr(workspace), workspace.numel() if workspace is not None else 0, _stream()),
-              "dj_conv2d_nhwc_fwd_t")
-        return y
-    if workspace is not None:
-        flags = int(bool(relu)) | (2 if y_zeroed else 0) | (4 if stats_may_split else 0)
-        check(_L().dj_conv2d_nhwc_fwd_ws(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),
-                                                int(pro_relu), flags, ptr(stats), ptr(workspace), workspace.numel(),
-                                                _stream()), "dj_conv2d_nhwc_fwd_ws")
-        return y
-    check(_L().dj_conv2d_nhwc_fwd(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),
-                                         int(pro_relu), int(bool(relu)) | (2 if y_zeroed else 0), ptr(stats), _stream()),
-          "dj_conv2d_nhwc_fwd")
-    return y
+    a = _lib.ConvFwdArgs(pro_relu=int(pro_relu), flags=int(bool(relu)) | (2 if y_zeroed else 0) | (4 if stats_may_split else 0))
+    return _fwd(_desc_for(desc, x, y), a, x, w, bias, y, pro_scale, pro_shift, stats, workspace)
 
 
 def conv2d_fwd_workspace_floats(desc, stats_may_split=False):
@@ -186,30 +192,9 @@ def conv2d_fwd_addrelu(desc, x, w, bias, y, pro_scale, pro_shift, res, res_scale
                        relu=False, stats=None, workspace=None):
     """1x1 stride-1 conv of relu(x*pro_scale+pro_shift + res*res_scale+res_shift); `sum_out` receives that input.
     `workspace`: as for conv2d_fwd."""
-    d = _desc_for(desc, x, y)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
-    assert tuple(res.shape) == tuple(x.shape) and (sum_out is None or tuple(sum_out.shape) == tuple(x.shape))
-    if any16(x, res, y, sum_out, w):
-        assert res.dtype == x.dtype, "the residual operand is read like x: same storage type"
-        check(_L().dj_conv2d_nhwc_fwd_t(d, ptr(x), dt_of(x), ptr(w), dt_of(w), ptr(bias), ptr(y), dt_of(y), ptr(pro_scale),
-                                               ptr(pro_shift), 1, int(relu), ptr(stats), ptr(res), _pixel_ld(res), ptr(res_scale),
-                                               ptr(res_shift), ptr(sum_out), _pixel_ld(sum_out) if sum_out is not None else 0,
-                                               dt_of(sum_out), ptr(workspace),
-                                               workspace.numel() if workspace is not None else 0, _stream()),
-              "dj_conv2d_nhwc_fwd_t")
-        return y
-    if workspace is not None:
-        check(_L().dj_conv2d_nhwc_fwd_addrelu_ws(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),
-                                                        ptr(res), _pixel_ld(res), ptr(res_scale), ptr(res_shift),
-                                                        ptr(sum_out), _pixel_ld(sum_out) if sum_out is not None else 0,
-                                                        int(relu), ptr(stats), ptr(workspace), workspace.numel(),
-                                                        _stream()), "dj_conv2d_nhwc_fwd_addrelu_ws")
-        return y
-    check(_L().dj_conv2d_nhwc_fwd_addrelu(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),
-                                                 ptr(res), _pixel_ld(res), ptr(res_scale), ptr(res_shift), ptr(sum_out),
-                                                 _pixel_ld(sum_out) if sum_out is not None else 0, int(relu), ptr(stats),
-                                                 _stream()), "dj_conv2d_nhwc_fwd_addrelu")
-    return y
+    a = _lib.ConvFwdArgs(pro_relu=1, flags=int(bool(relu)))
+    _residual(a, x, res, res_scale, res_shift, sum_out)
+    return _fwd(_desc_for(desc, x, y), a, x, w, bias, y, pro_scale, pro_shift, stats, workspace)
 
 
 BN_ACC_REPLICAS = 16   # DJ_BN_ACC_REPLICAS of include/dj_hip.h
@@ -227,25 +212,26 @@ def conv2d_fwd_bn(desc, x, w, bias, y, bn, pro_scale=None, pro_shift=None, pro_r
                   res_shift=None, sum_out=None):
     """Forward conv + the training-mode BatchNormalization statistics / coefficients of its output in one launch."""
     import ctypes
-    assert not any16(x, w, y, res, sum_out), "conv2d_fwd_bn has no `_t` entry point: every tensor must be torch.float32"
-    d = _desc_for(desc, x, y)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
-    check(_L().dj_conv2d_nhwc_fwd_bn(d, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(pro_scale), ptr(pro_shift),
-                                            int(pro_relu), ptr(res), _pixel_ld(res) if res is not None else 0,
-                                            ptr(res_scale), ptr(res_shift), ptr(sum_out),
-                                            _pixel_ld(sum_out) if sum_out is not None else 0, ctypes.byref(bn), _stream()),
-          "dj_conv2d_nhwc_fwd_bn")
-    return y
+    assert not any16(x, w, y, res, sum_out), "conv2d_fwd_bn: the fused finalize is fp32 only, every tensor must be torch.float32"
+    a = _lib.ConvFwdArgs(pro_relu=int(pro_relu), bn=ctypes.pointer(bn))
+    if res is not None:
+        _residual(a, x, res, res_scale, res_shift, sum_out)
+    return _fwd(_desc_for(desc, x, y), a, x, w, bias, y, pro_scale, pro_shift, None, None)
+
+
+def _dgrad(desc, a, dy, w, bias, dx):
+    d = _desc_for(desc, dx, dy)
+    assert _weights_ok(w, d)
+    a.dy, a.dt_dy, a.w, a.dt_w, a.bias, a.dx, a.dt_dx = ptr(dy), dt_of(dy), ptr(w), dt_of(w), ptr(bias), ptr(dx), dt_of(dx)
+    check(_L().dj_conv2d_nhwc_dgrad(d, a, _stream()), "dj_conv2d_nhwc_dgrad")
+    return dx
 
 
 def _dgrad_relumask(desc, dy, w, dx, relu_mask, bias, beta):
-    d = _desc_for(desc, dx, dy)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
     assert not any16(dy, dx, w, relu_mask), "conv2d_dgrad(relu_mask=...): every tensor must be torch.float32"
     assert tuple(relu_mask.shape) == tuple(dx.shape)
-    check(_L().dj_conv2d_nhwc_dgrad_relumask(d, ptr(dy), ptr(w), ptr(bias), ptr(dx), int(bool(beta)), ptr(relu_mask),
-                                             _pixel_ld(relu_mask), _stream()), "dj_conv2d_nhwc_dgrad_relumask")
-    return dx
+    a = _lib.ConvDgradArgs(flags=int(bool(beta)), mask_x=ptr(relu_mask), ld_mask=_pixel_ld(relu_mask))
+    return _dgrad(desc, a, dy, w, bias, dx)
 
 
 def conv2d_dgrad_relumask_supported(desc):
@@ -256,20 +242,10 @@ def conv2d_dgrad(desc, dy, w, dx, bias=None, beta=False, no_split=False, relu_ma
     """`no_split`: one K range per tile (no fp32 atomics): for the forward use as Conv2DTranspose.
     `relu_mask` (a tensor shaped like dx: the convolution's forward input x = relu(...)): the epilogue stores
     `relu_mask > 0 ? value : 0` -- the input gradient and the ReLU backward of x in one launch
-    (dj_conv2d_nhwc_dgrad_relumask; fp32 tensors, one K range)."""
+    (dj_conv_dgrad_args.mask_x; fp32 tensors, one K range)."""
     if relu_mask is not None:
         return _dgrad_relumask(desc, dy, w, dx, relu_mask, bias, beta)
-    d = _desc_for(desc, dx, dy)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
-    if any16(dy, dx, w):
-        check(_L().dj_conv2d_nhwc_dgrad_t(d, ptr(dy), dt_of(dy), ptr(w), dt_of(w), ptr(bias), ptr(dx), dt_of(dx),
-                                                 int(bool(beta)) | (2 if no_split else 0), None, 0, 0, None, None, None, None,
-                                                 None, _stream()), "dj_conv2d_nhwc_dgrad_t")
-        return dx
-    check(_L().dj_conv2d_nhwc_dgrad(d, ptr(dy), ptr(w), ptr(bias), ptr(dx), int(bool(beta)) | (2 if no_split else 0),
-                                           _stream()),
-          "dj_conv2d_nhwc_dgrad")
-    return dx
+    return _dgrad(desc, _lib.ConvDgradArgs(flags=int(bool(beta)) | (2 if no_split else 0)), dy, w, bias, dx)
 
 
 def conv2d_dgrad_relumask(desc, dy, w, dx, relu_mask, bias=None, beta=False):
@@ -281,33 +257,22 @@ def conv2d_dgrad_relumask(desc, dy, w, dx, relu_mask, bias=None, beta=False):
 
 
 def conv2d_dgrad_bnbwd(desc, dy, w, dx, z, mean, invstd, scale, shift, partial):
-    """Input gradient + BatchNormalization backward statistics of dx in the same launch (dj_conv2d_nhwc_dgrad_bnbwd):
+    """Input gradient + BatchNormalization backward statistics of dx in the same launch (dj_conv_dgrad_args.partial):
     `partial` [ceil(rows / 64)][2][in_c] receives what dj_bn_bwd_reduce would compute from (dx, z)."""
-    d = _desc_for(desc, dx, dy)
-    assert w.is_contiguous() and tuple(w.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
     assert tuple(z.shape) == tuple(dx.shape)
-    rows = d.batch * d.in_h * d.in_w
-    assert partial.is_contiguous() and tuple(partial.shape) == ((rows + 63) // 64, 2, d.in_c)
-    if any16(dy, dx, z, w):
-        check(_L().dj_conv2d_nhwc_dgrad_t(d, ptr(dy), dt_of(dy), ptr(w), dt_of(w), None, ptr(dx), dt_of(dx), 2, ptr(z), _pixel_ld(z),
-                                                 dt_of(z), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(partial),
-                                                 _stream()), "dj_conv2d_nhwc_dgrad_t")
-        return dx
-    check(_L().dj_conv2d_nhwc_dgrad_bnbwd(d, ptr(dy), ptr(w), ptr(dx), ptr(z), _pixel_ld(z), ptr(mean), ptr(invstd),
-                                                 ptr(scale), ptr(shift), ptr(partial), _stream()),
-          "dj_conv2d_nhwc_dgrad_bnbwd")
-    return dx
+    rows = desc.batch * desc.in_h * desc.in_w
+    assert partial.is_contiguous() and tuple(partial.shape) == ((rows + 63) // 64, 2, desc.in_c)
+    a = _lib.ConvDgradArgs(flags=2, z=ptr(z), ld_z=_pixel_ld(z), dt_z=dt_of(z), mean=ptr(mean), invstd=ptr(invstd),
+                           scale=ptr(scale), shift=ptr(shift), partial=ptr(partial))
+    return _dgrad(desc, a, dy, w, None, dx)
 
 
 def conv2d_wgrad(desc, x, dy, dw, pro_scale=None, pro_shift=None, pro_relu=False, dw_zeroed=False):
     d = _desc_for(desc, x, dy)
-    assert dw.is_contiguous() and tuple(dw.shape) == (d.kernel_h, d.kernel_w, d.in_c, d.out_c)
-    if any16(x, dy):
-        check(_L().dj_conv2d_nhwc_wgrad_t(d, ptr(x), dt_of(x), ptr(dy), dt_of(dy), ptr(dw), ptr(pro_scale), ptr(pro_shift),
-                                                 int(pro_relu), int(dw_zeroed), _stream()), "dj_conv2d_nhwc_wgrad_t")
-        return dw
-    check(_L().dj_conv2d_nhwc_wgrad(d, ptr(x), ptr(dy), ptr(dw), ptr(pro_scale), ptr(pro_shift),
-                                           int(pro_relu), int(dw_zeroed), _stream()), "dj_conv2d_nhwc_wgrad")
+    assert _weights_ok(dw, d)
+    a = _lib.ConvWgradArgs(ptr(x), dt_of(x), ptr(dy), dt_of(dy), ptr(dw), ptr(pro_scale), ptr(pro_shift), int(pro_relu),
+                           int(dw_zeroed))
+    check(_L().dj_conv2d_nhwc_wgrad(d, a, _stream()), "dj_conv2d_nhwc_wgrad")
     return dw
 
 

@@ -20,7 +20,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), "library does not export " + name
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
-    assert lib.dj_abi_version() == _lib.ABI_VERSION == 3
+    assert lib.dj_abi_version() == _lib.ABI_VERSION == 4
     assert lib.dj_reduce_rows(46208) == 722
 
 
@@ -37,24 +37,68 @@ def test_conv_desc_argument_errors_surface_through_the_abi():
 
 
 def test_dgrad_with_bn_backward_statistics_refuses_what_it_cannot_do():
-    """dj_conv2d_nhwc_dgrad_bnbwd checks its arguments on the host, before any launch: missing tensors, scale without
-    shift, a z pitch below the channel count, and strided 1x1 convolutions (their dx is scattered, the accumulator tile is
-    not the gradient tile)."""
+    """dj_conv2d_nhwc_dgrad with `partial` checks its arguments on the host, before any launch: missing tensors, scale
+    without shift, a z pitch below the channel count, and strided 1x1 convolutions (their dx is scattered, the accumulator
+    tile is not the gradient tile)."""
     import ctypes
     from jpeg_detection_resnet_ssd_amd import _lib
     lib = _lib.load()
     fake = 0x1000      # never dereferenced: every call below must fail in the argument checks
     ok = _lib.ConvDesc(2, 8, 8, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 1, 1, 32, 64)
-    call = lib.dj_conv2d_nhwc_dgrad_bnbwd
-    assert call(ctypes.byref(ok), fake, fake, fake, None, 32, fake, fake, fake, fake, fake, None) < 0
+
+    def call(d, z, ld_z, scale, shift):
+        a = _lib.ConvDgradArgs(dy=fake, w=fake, dx=fake, z=z, ld_z=ld_z, mean=fake, invstd=fake, scale=scale, shift=shift,
+                               partial=fake)
+        return lib.dj_conv2d_nhwc_dgrad(ctypes.byref(d), ctypes.byref(a), None)
+    assert call(ok, None, 32, fake, fake) < 0          # statistics requested but z missing: no silent plain input gradient
     assert b"null" in lib.dj_last_error()
-    assert call(ctypes.byref(ok), fake, fake, fake, fake, 32, fake, fake, fake, None, fake, None) < 0
+    assert call(ok, fake, 32, fake, None) < 0
     assert b"scale/shift" in lib.dj_last_error()
-    assert call(ctypes.byref(ok), fake, fake, fake, fake, 16, fake, fake, None, None, fake, None) < 0
+    assert call(ok, fake, 16, None, None) < 0
     assert b"ld_z" in lib.dj_last_error()
     strided = _lib.ConvDesc(2, 8, 8, 32, 4, 4, 64, 1, 1, 2, 2, 1, 1, 0, 0, 32, 64)
-    assert call(ctypes.byref(strided), fake, fake, fake, fake, 32, fake, fake, None, None, fake, None) < 0
+    assert call(strided, fake, 32, None, None) < 0
     assert b"strided" in lib.dj_last_error()
+
+
+def test_conv_entry_points_refuse_bad_argument_structs():
+    """The three convolution entry points check their argument struct on the host, before any launch: options that do not
+    go together, storage codes they do not know or cannot take in the calling thread's arithmetic mode, bad sizes."""
+    import ctypes
+    from jpeg_detection_resnet_ssd_amd import _lib
+    lib = _lib.load()
+    fake = 0x1000      # never dereferenced: every call below must fail in the argument checks
+    c3 = _lib.ConvDesc(2, 8, 8, 32, 8, 8, 64, 3, 3, 1, 1, 1, 1, 1, 1, 32, 64)
+    c1 = _lib.ConvDesc(2, 8, 8, 32, 8, 8, 64, 1, 1, 1, 1, 1, 1, 0, 0, 32, 64)
+
+    def refused(fn, d, a, word):
+        assert fn(ctypes.byref(d), ctypes.byref(a), None) < 0
+        assert word in lib.dj_last_error(), lib.dj_last_error()
+
+    def fwd(**kw):
+        return _lib.ConvFwdArgs(x=fake, w=fake, y=fake, **kw)
+    refused(lib.dj_conv2d_nhwc_fwd, c1, fwd(sum_out=fake, ld_sum=32), b"sum_out without res")
+    refused(lib.dj_conv2d_nhwc_fwd, c3, fwd(res=fake, ld_res=32, pro_scale=fake, pro_shift=fake), b"1x1")
+    refused(lib.dj_conv2d_nhwc_fwd, c3, fwd(workspace=fake, workspace_floats=-1), b"workspace")
+    refused(lib.dj_conv2d_nhwc_fwd, c3, fwd(dt_x=7), b"unknown storage type")
+    bn = _lib.BnTrain(*([fake] * 10), 1e-3, 0.99)
+    prev = lib.dj_set_thread_compute_mode(0)
+    try:
+        refused(lib.dj_conv2d_nhwc_fwd, c3, fwd(dt_x=1), b"arithmetic mode 1")
+        lib.dj_set_thread_compute_mode(1)
+        refused(lib.dj_conv2d_nhwc_fwd, c3, fwd(dt_y=1, bn=ctypes.pointer(bn)), b"BatchNormalization")
+    finally:
+        lib.dj_set_thread_compute_mode(prev)
+
+    def dgrad(**kw):
+        return _lib.ConvDgradArgs(dy=fake, w=fake, dx=fake, **kw)
+    stats = dict(z=fake, ld_z=32, mean=fake, invstd=fake, partial=fake)
+    refused(lib.dj_conv2d_nhwc_dgrad, c3, dgrad(bias=fake, **stats), b"bias")
+    refused(lib.dj_conv2d_nhwc_dgrad, c3, dgrad(flags=1, **stats), b"accumulating")
+    refused(lib.dj_conv2d_nhwc_dgrad, c3, dgrad(mask_x=fake, ld_mask=32, **stats), b"ReLU mask")
+    refused(lib.dj_conv2d_nhwc_dgrad, c3, dgrad(mask_x=fake, ld_mask=16), b"ld_mask")
+
+    refused(lib.dj_conv2d_nhwc_wgrad, c3, _lib.ConvWgradArgs(x=fake, dy=fake, dw=fake, dt_dy=3), b"unknown storage type")
 
 
 def test_same_padding_rule():

@@ -74,7 +74,7 @@ def test_bottleneck_blocks(kind, cuda, monkeypatch):
         monkeypatch.setenv("DJ_AUTOTUNE", "1")
         kind = kind[:-len("+autotune")]
     if kind.endswith("+bnfin"):
-        # opt-in lowering: the convs finalize their BatchNormalization themselves (dj_conv2d_nhwc_fwd_bn)
+        # opt-in lowering: the convs finalize their BatchNormalization themselves (dj_conv_fwd_args.bn)
         monkeypatch.setenv("DJ_FUSE_BNFIN", "1")
         kind = kind[:-len("+bnfin")]
     from jpeg_detection_resnet_ssd_amd.keras import backend as K

@@ -227,7 +227,7 @@ SLAB_CASES = [
 
 @pytest.mark.parametrize("case", SLAB_CASES)
 def test_split_forward_through_slabs_is_exact_and_reproducible(case, cuda):
-    """dj_conv2d_nhwc_fwd_ws: a split-K forward launch stores its partial tiles to the caller's workspace and a second
+    """dj_conv2d_nhwc_fwd with a workspace: a split-K forward launch stores its partial tiles to the caller's workspace and a second
     kernel adds them in a fixed order (+ bias, ReLU, BatchNormalization statistics).  Every tile variant, splits 1 / 2 /
     5: result against the fp64 oracle, statistics against the result, and two launches bit-identical (the path without
     workspace accumulates with atomics and is not).  Too small a workspace: atomics again, or -- when the statistics
@@ -291,7 +291,7 @@ def test_split_forward_through_slabs_is_exact_and_reproducible(case, cuda):
 @pytest.mark.parametrize("geom", [(3, 19, 19, 256, 64), (2, 38, 38, 64, 256), (2, 10, 10, 512, 128), (1, 5, 5, 96, 32)])
 @pytest.mark.parametrize("res_affine", [False, True])
 def test_fwd_with_residual_add_prologue(geom, res_affine, cuda):
-    """dj_conv2d_nhwc_fwd_addrelu: conv1x1(relu(bn(z) + shortcut)) in one launch, the sum written as a by-product,
+    """dj_conv2d_nhwc_fwd with `res`: conv1x1(relu(bn(z) + shortcut)) in one launch, the sum written as a by-product,
     BN statistics of the conv output in the epilogue -- every tile variant."""
     from jpeg_detection_resnet_ssd_amd import _lib
     from jpeg_detection_resnet_ssd_amd import kernels as K
@@ -330,7 +330,7 @@ def test_fwd_with_residual_add_prologue(geom, res_affine, cuda):
 @pytest.mark.parametrize("geom", [(3, 19, 19, 96, 128, 3), (2, 38, 38, 64, 256, 1), (4, 10, 10, 256, 64, 1),
                                   (8, 75, 75, 64, 64, 1)])   # the last one spreads over 5 accumulator replicas
 def test_fwd_with_fused_batchnorm_finalize(geom, cuda):
-    """dj_conv2d_nhwc_fwd_bn: scale / shift / saved and moving statistics written by the conv launch itself (fp64 atomics
+    """dj_conv2d_nhwc_fwd with `bn`: scale / shift / saved and moving statistics written by the conv launch itself (fp64 atomics
     + last-workgroup ticket) == conv statistics + dj_bn_train_finalize, for every tile variant, twice in a row (the
     accumulators and the ticket must be left clean)."""
     from jpeg_detection_resnet_ssd_amd import _lib
@@ -378,7 +378,7 @@ def test_fwd_with_fused_batchnorm_finalize(geom, cuda):
                                   (5, 10, 10, 320, 128, 3, "same"), (1, 5, 5, 64, 96, 1, "valid")])
 @pytest.mark.parametrize("masked", [True, False])
 def test_dgrad_takes_bn_backward_statistics(geom, masked, cuda):
-    """dj_conv2d_nhwc_dgrad_bnbwd: the input gradient g of a convolution whose input is relu(bn(z)) (or bn(z)) and, from the
+    """dj_conv2d_nhwc_dgrad with `partial`: the input gradient g of a convolution whose input is relu(bn(z)) (or bn(z)) and, from the
     same launch, the BatchNormalization backward sums over g and z -- every tile variant; dx identical to the plain
     launch, column totals of the partial rows against fp64 and against dj_bn_bwd_reduce on the stored dx."""
     from jpeg_detection_resnet_ssd_amd import _lib, engine

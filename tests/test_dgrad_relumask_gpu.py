@@ -1,4 +1,4 @@
-"""dj_conv2d_nhwc_dgrad_relumask (kernels.conv2d_dgrad(relu_mask=...)): the input gradient whose epilogue applies the ReLU mask
+"""dj_conv2d_nhwc_dgrad with `mask_x` (kernels.conv2d_dgrad(relu_mask=...)): the input gradient whose epilogue applies the ReLU mask
 of the tensor it differentiates, against the two launches it replaces -- the plain (accumulating) input gradient followed by
 dj_relu_bwd in place, on the same previous contents of dx.  One K range per tile in both, the same tile variant, the same
 accumulation order: the results must agree BIT FOR BIT, under every tile variant the tuner may register and in every

@@ -80,7 +80,7 @@ def test_fit_generator_with_the_trainers_callbacks(cuda, tmp_path):
     probe.set_weights_dict(saved, strict=True)
     # same weights, two models: bit-identical predictions.  (The forward pass has no arrival-order arithmetic: split-K
     # launches -- fc6 with K = 18432, the small maps behind it -- go through slabs and a fixed-order reduction,
-    # dj_conv2d_nhwc_fwd_ws; until round 2 they used fp32 atomics and only the 38x38 source was reproducible.)
+    # the workspace of dj_conv2d_nhwc_fwd; until round 2 they used fp32 atomics and only the 38x38 source was reproducible.)
     a, b = fresh.predict(x, batch_size=BATCH), probe.predict(x, batch_size=BATCH)
     np.testing.assert_array_equal(a, b)
     np.testing.assert_array_equal(a, fresh.predict(x, batch_size=BATCH))

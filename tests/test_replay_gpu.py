@@ -185,7 +185,7 @@ class Replay(object):
 
     def dgrad_bnbwd(self, orig):
         """Input gradient whose epilogue also takes the BatchNormalization backward sums of the tensor it writes
-        (dj_conv2d_nhwc_dgrad_bnbwd): dx against the oracle, the column totals of the partial rows against fp64 sums over
+        (dj_conv_dgrad_args.partial): dx against the oracle, the column totals of the partial rows against fp64 sums over
         (dx, z) on their natural scale.  (dgamma / dbeta / dz of that layer are checked again where its apply pass runs.)"""
         def run(desc, dy, w, dx, z, mean, invstd, scale, shift, partial):
             key = ("dgrad", self._geom(desc), "bnbwd", scale is not None, str(dy.dtype), str(dx.dtype), str(z.dtype))

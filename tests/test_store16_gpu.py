@@ -1,5 +1,5 @@
 """BASELINE config 5 proper: activations held as fp16 and their gradients as bf16 in HBM (K.set_floatx('float16'),
-include/dj_hip.h `_t` entry points).  Every check feeds the kernel the ROUNDED tensors and compares with the fp64 oracle
+include/dj_hip.h storage-type codes and `_t` entry points).  Every check feeds the kernel the ROUNDED tensors and compares with the fp64 oracle
 on those same rounded values, so what is measured is the kernel's own error: operand rounding inside the GEMM (fp16
 forward 1.5e-3, bf16 gradients 8e-3 rel-L2, the tolerances of tests/test_lowp_gpu.py) plus ONE storage rounding where a
 16-bit tensor is written (fp16 2^-11 = 4.9e-4, bf16 2^-8 = 3.9e-3 per element, so <= 5e-4 / 4e-3 rel-L2)."""
@@ -209,7 +209,7 @@ def test_weight_gradient_with_16bit_tensors_every_variant(geom, x_dt, dy_dt, flo
 
 def test_typed_launches_are_refused_outside_their_domain(floatx):
     """A 16-bit tensor never goes through a silent conversion or the generic kernel: channel counts the branch-free
-    kernels cannot take, a strided 3x3 input gradient, the exact-fp32 mode and a wrapper without a `_t` entry point are
+    kernels cannot take, a strided 3x3 input gradient, the exact-fp32 mode and the fp32-only fused BatchNormalization finalize are
     errors."""
     from jpeg_detection_resnet_ssd_amd import _lib
     from jpeg_detection_resnet_ssd_amd import kernels as Kn
@@ -231,8 +231,7 @@ def test_typed_launches_are_refused_outside_their_domain(floatx):
     y3 = torch.zeros(2, 8, 8, 64, device="cuda")
     with pytest.raises(_lib.DjError, match="mode 1"):
         Kn.conv2d_fwd(Kn.make_conv_desc(2, 8, 8, 64, 64, (1, 1)), x3, w3, None, y3)
-    # conv + BatchNormalization coefficients in one launch has a float entry point only: a 16-bit x, y or residual operand
-    # would be read as fp32
+    # conv + BatchNormalization coefficients in one launch is fp32 only: the wrapper refuses a 16-bit x, y or residual operand
     co = [torch.zeros(64, device="cuda") for _ in range(8)]
     bn = Kn.make_bn_train(torch.zeros(Kn.BN_ACC_REPLICAS * 2 * 64, dtype=torch.float64, device="cuda"),
                           torch.zeros(1, dtype=torch.int32, device="cuda"), *co, 1e-3, 0.99)

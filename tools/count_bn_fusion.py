@@ -1,5 +1,5 @@
 """How many BatchNormalization backward passes of a workload's training plan take their statistics from the producing
-input-gradient GEMM (dj_conv2d_nhwc_dgrad_bnbwd) and how many still launch dj_bn_bwd_reduce.  python tools/count_bn_fusion.py deconv 32 [floatx]"""
+input-gradient GEMM (kernels.conv2d_dgrad_bnbwd) and how many still launch dj_bn_bwd_reduce.  python tools/count_bn_fusion.py deconv 32 [floatx]"""
 import os, sys, collections
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,7 +20,7 @@ def call(name, *a):
     counts[name] += 1
     return real_call(name, *a)
 def fused(desc, *a):
-    counts["dj_conv2d_nhwc_dgrad_bnbwd"] += 1
+    counts["conv2d_dgrad_bnbwd"] += 1
     counts["fused %dx%d %d->%d k%d" % (desc.in_h, desc.in_w, desc.out_c, desc.in_c, desc.kernel_h)] += 1
     return real_fused(desc, *a)
 L.call, Kn.conv2d_dgrad_bnbwd = call, fused

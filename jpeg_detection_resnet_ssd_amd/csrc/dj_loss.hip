@@ -6,6 +6,7 @@
 // classification_part/config/resnet/config_file.py:58-65 (SGD, categorical_crossentropy).
 #include "../../include/dj_hip.h"
 #include "dj_common.h"
+#include <atomic>
 
 static inline int ew_blocks(long total) {
   long b = (total + 255) / 256;
@@ -489,11 +490,29 @@ extern "C" int dj_categorical_crossentropy(const float* y_true, const float* pro
 // ---------------------------------------------------------------------------------
 // keras.optimizers.SGD:  g' = g*grad_scale + 2*l2*p ; v = momentum*v - lr_t*g' ;
 //                        p += nesterov ? momentum*v - lr_t*g' : v
-// Optionally accumulates sum(p^2) (pre-update) into sumsq[0] for the l2 penalty report.
+// Optionally accumulates sum(p^2) (pre-update) into sumsq[0] for the l2 penalty report.  The workgroups add their sums in
+// fp64 to an accumulator of the library and take a ticket; the one that takes the last adds the total to sumsq[0], in ONE
+// fp32 addition, and clears both (the ticket scheme of the BatchNormalization statistics in dj_igemm.h).  An fp32 atomic per
+// workgroup on sumsq[0] itself rounded the running total up to 4096 times: 0.7e-6 .. 2e-6 of the sum at a million elements,
+// different from run to run.  Launches that may be in flight together must not share an accumulator: the launcher hands
+// out DJ_SGD_SLOTS of them in turn.  The workgroups spread their sums over DJ_SGD_REPLICAS copies, each on a 128-byte line
+// of its own like the ticket, so that no line takes more atomics than sumsq[0] took.
 // ---------------------------------------------------------------------------------
+#define DJ_SGD_SLOTS 64
+#define DJ_SGD_REPLICAS 8
+struct DjSgdSlot {
+  struct {
+    double v;
+    double pad[15];
+  } acc[DJ_SGD_REPLICAS];
+  unsigned ticket;
+  unsigned pad[31];
+};
+__device__ DjSgdSlot dj_sgd_slots[DJ_SGD_SLOTS];
+
 __global__ __launch_bounds__(256) void dj_sgd_kernel(float* p, const float* g, float* v, long n, float lr_t,
                                                       float momentum, int nesterov, float l2, float grad_scale,
-                                                      float* sumsq) {
+                                                      float* sumsq, int slot) {
   float acc = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float pi = p[i];
@@ -509,7 +528,22 @@ __global__ __launch_bounds__(256) void dj_sgd_kernel(float* p, const float* g, f
     __shared__ float red[4];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(sumsq, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+      DjSgdSlot* s = &dj_sgd_slots[slot];
+      atomicAdd(&s->acc[blockIdx.x % DJ_SGD_REPLICAS].v,
+                ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]));
+      // the ticket after the sum has been performed: device-scope atomics are complete when vmcnt reaches zero
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (atomicAdd(&s->ticket, 1u) == gridDim.x - 1u) {
+        double total = 0.0;
+        for (int r = 0; r < DJ_SGD_REPLICAS; ++r) {
+          total += __hip_atomic_load(&s->acc[r].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(&s->acc[r].v, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __hip_atomic_store(&s->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        atomicAdd(sumsq, (float)total);
+      }
+    }
   }
 }
 
@@ -517,8 +551,10 @@ extern "C" int dj_sgd_momentum_update(float* param, const float* grad, float* ve
                                       float momentum, int nesterov, float l2, float grad_scale, float* sumsq,
                                       void* stream) {
   DJ_CHECK_ARG(param && grad && velocity && n > 0, "sgd: bad arguments");
+  static std::atomic<unsigned> next_slot{0};
+  const int slot = sumsq ? (int)(next_slot.fetch_add(1u) % DJ_SGD_SLOTS) : 0;
   hipLaunchKernelGGL(dj_sgd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, velocity, n,
-                     lr_t, momentum, nesterov, l2, grad_scale, sumsq);
+                     lr_t, momentum, nesterov, l2, grad_scale, sumsq, slot);
   DJ_CHECK_LAUNCH("dj_sgd_momentum_update");
   return DJ_OK;
 }

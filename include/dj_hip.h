@@ -405,6 +405,33 @@ int dj_categorical_crossentropy(const float* y_true, const float* probs, long ro
 int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, long n, float lr_t, float momentum,
                            int nesterov, float l2, float grad_scale, float* sumsq, void* stream);
 
+/* ---- keras.optimizers.Adam.get_updates and Adadelta.get_updates (Keras 2.2.4; L/evaluation.py:102, L/inference.py:104 build
+ * Adam(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-08, decay=0.0); C/template_keras/config/template_config.py imports
+ * Adadelta).  keras/optimizers.py states both in numpy (adam_host, adadelta_host); the entry points equal that statement
+ * bit for bit: fp32 throughout, every operation rounded once in the order written, no fma.  Both share the head of
+ * dj_sgd_momentum_update, the l2 kernel_regularizer gradient and the data-parallel 1/world_size:
+ *     g' = g * grad_scale + (2 * l2) * p
+ * dj_adam_update:      m = beta_1 * m + (1 - beta_1) * g';   v = beta_2 * v + (1 - beta_2) * (g' * g')
+ *                      vhat != NULL (amsgrad): vhat = max(vhat, v), a NaN on either side giving NaN, and d = vhat; else d = v
+ *                      p = p - (lr_t * m) / (sqrt(d) + epsilon)
+ *   with 1 - beta in fp32 and lr_t = lr / (1 + decay * iterations) * sqrt(1 - beta_2^t) / (1 - beta_1^t), t = iterations + 1,
+ *   computed by the caller (Adam.step_size()).
+ * dj_adadelta_update:  a = rho * a + one_minus_rho * (g' * g');   u = (g' * sqrt(d + epsilon)) / sqrt(a + epsilon)
+ *                      p = p - lr * u;   d = rho * d + one_minus_rho * (u * u)
+ *   with lr = lr / (1 + decay * iterations) and one_minus_rho = (float)(1.0 - rho), subtracted in double as Keras does with
+ *   its Python float, both computed by the caller.
+ * sumsq != NULL: sumsq[0] += sum(p^2) before the update, as dj_sgd_momentum_update reports it.  One thread per four
+ * consecutive elements in a grid-stride loop of at most dj_optim_groups_per_pass() threads; 16-byte accesses when every
+ * pointer is 16-byte aligned, element by element otherwise.  DJ_ERR_ARG for a null pointer (vhat and sumsq excepted),
+ * n <= 0, or buffers that overlap. ---- */
+long dj_optim_groups_per_pass(void);
+int dj_adam_update(float* param, const float* grad, float* m, float* v, float* vhat /* NULL: no amsgrad */, long n,
+                   float lr_t, float beta_1, float beta_2, float epsilon, float l2, float grad_scale,
+                   float* sumsq /* may be NULL */, void* stream);
+int dj_adadelta_update(float* param, const float* grad, float* accum, float* delta_accum, long n, float lr, float rho,
+                       float one_minus_rho, float epsilon, float l2, float grad_scale, float* sumsq /* may be NULL */,
+                       void* stream);
+
 /* ---- DecodeDetections (L/keras_layers/keras_layer_DecodeDetections.py:109-265; numpy twin
  * L/ssd_encoder_decoder/ssd_output_decoder.py:111-226): y_pred [batch][n_boxes][n_classes+12] (centroid offsets, anchors,
  * variances in the last 12 columns) -> out [batch][top_k][6] = (class, confidence, xmin, ymin, xmax, ymax) sorted by

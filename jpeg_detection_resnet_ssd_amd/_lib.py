@@ -174,6 +174,11 @@ SIGNATURES = {
     "dj_ssd_loss_bwd": (c_int, [FP, FP, c_long, c_int, c_float, c_float, FP, FP, FP, c_void_p]),
     "dj_categorical_crossentropy": (c_int, [FP, FP, c_long, c_int, c_float, FP, FP, FP, c_void_p]),
     "dj_sgd_momentum_update": (c_int, [FP, FP, FP, c_long, c_float, c_float, c_int, c_float, c_float, FP, c_void_p]),
+    "dj_optim_groups_per_pass": (c_long, []),
+    "dj_adam_update": (c_int, [FP, FP, FP, FP, FP, c_long, c_float, c_float, c_float, c_float, c_float, c_float, FP,
+                               c_void_p]),
+    "dj_adadelta_update": (c_int, [FP, FP, FP, FP, c_long, c_float, c_float, c_float, c_float, c_float, c_float, FP,
+                                   c_void_p]),
     "dj_decode_detections_workspace_floats": (c_long, [c_int, c_int, c_int, c_int]),
     "dj_decode_detections": (c_int, [FP, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, FP, FP,
                                      c_void_p]),

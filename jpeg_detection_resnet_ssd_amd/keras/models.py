@@ -233,13 +233,13 @@ class Model(object):
 
     # ---- compile ----------------------------------------------------------------------
     def compile(self, optimizer, loss=None, metrics=None, **kwargs):
-        if isinstance(optimizer, str):
-            if optimizer.lower() != "sgd":
-                raise NotImplementedError("optimizer %r" % optimizer)
-            optimizer = optimizers.SGD()
-        if not isinstance(optimizer, optimizers.SGD):
-            raise NotImplementedError("only keras.optimizers.SGD is on the reference's hot path")
+        optimizer = optimizers.get(optimizer)
+        if self.optimizer is not None and type(optimizer) is not type(self.optimizer) and self._store is not None:
+            # an optimizer of another kind starts from zeroed state, as a fresh Keras optimizer does
+            self._store.pop("opt_state", None)
+            self._store["vel"].zero_()
         self.optimizer = optimizer
+        optimizer._bind(self)
         self.metrics = list(metrics or [])
         owner = getattr(loss, "__self__", None)
         if owner is not None and hasattr(owner, "_dj_loss"):
@@ -458,18 +458,75 @@ class Model(object):
         """`plan`: the training plan whose backward pass just ran (data parallel: it must carry the gradient exchange;
         None = the plan of the last run_train_step)."""
         st, opt = self._store, self.optimizer
-        lr_t = opt.current_lr()
         scale = 1.0
         if self.dist is not None:
             scale = self.dist.finish_gradients(plan if plan is not None else self._last_train_plan)
+        if isinstance(opt, optimizers.SGD):
+            lr_t = opt.current_lr()
+
+            def update(a, b, l2, ssq):
+                call("dj_sgd_momentum_update", st["flat"][a:b], st["grads"][a:b], st["vel"][a:b], b - a, lr_t,
+                     opt.momentum, int(opt.nesterov), l2, scale, ssq)
+        elif isinstance(opt, optimizers.Adam):
+            lr_t = opt.step_size()
+            m, v = self._optimizer_buffer("ms"), self._optimizer_buffer("vs")
+            vhat = self._optimizer_buffer("vhats") if opt.amsgrad else None
+
+            def update(a, b, l2, ssq):
+                call("dj_adam_update", st["flat"][a:b], st["grads"][a:b], m[a:b], v[a:b],
+                     vhat[a:b] if vhat is not None else None, b - a, lr_t, opt.beta_1, opt.beta_2, opt.epsilon, l2, scale,
+                     ssq)
+        else:
+            lr_t = opt.current_lr()
+            acc, dacc = self._optimizer_buffer("accumulators"), self._optimizer_buffer("delta_accumulators")
+
+            def update(a, b, l2, ssq):
+                call("dj_adadelta_update", st["flat"][a:b], st["grads"][a:b], acc[a:b], dacc[a:b], b - a, lr_t, opt.rho,
+                     1.0 - opt.rho, opt.epsilon, l2, scale, ssq)
         st["sumsq"].zero_()
         for i, (a, b, l2) in enumerate(st["segments"]):
             if b <= a:
                 continue
-            ssq = st["sumsq"][i:i + 1] if l2 else None
-            call("dj_sgd_momentum_update", st["flat"][a:b], st["grads"][a:b], st["vel"][a:b], b - a, lr_t,
-                 opt.momentum, int(opt.nesterov), l2, scale, ssq)
+            update(a, b, l2, st["sumsq"][i:i + 1] if l2 else None)
         opt.iterations += 1
+
+    # ---- optimizer state (Optimizer.get_weights / set_weights) -----------------------------
+    def _optimizer_buffer(self, name):
+        """The flat fp32 state buffer `name` of the compiled optimizer, n_train elements laid out like `flat`; SGD's
+        'moments' is the velocity buffer, the others are allocated zeroed when first asked for."""
+        self._ensure_params()
+        st = self._store
+        if name == "moments":
+            return st["vel"]
+        bufs = st.setdefault("opt_state", {})
+        if name not in bufs:
+            bufs[name] = torch.zeros(st["n_train"], dtype=torch.float32, device=self._device)
+        return bufs[name]
+
+    def _placeholder_state(self, name):
+        """Keras 2.2.4 keeps Adam's vhats as one zeros(1) per weight when amsgrad is off."""
+        return name == "vhats" and not self.optimizer.amsgrad
+
+    def _optimizer_state_shapes(self, name):
+        return [(1,) if self._placeholder_state(name) else tuple(w.shape) for w in self.weight_specs if w.trainable]
+
+    def _optimizer_state_arrays(self, name):
+        train = [w for w in self.weight_specs if w.trainable]
+        if self._placeholder_state(name):
+            return [np.zeros(1, np.float32) for _ in train]
+        host = self._optimizer_buffer(name).detach().cpu().numpy()
+        offs = self._store["offsets"]
+        return [host[offs[id(w)]:offs[id(w)] + w.size].reshape(w.shape).copy() for w in train]
+
+    def _set_optimizer_state_arrays(self, name, arrays):
+        if self._placeholder_state(name):
+            return
+        buf, offs = self._optimizer_buffer(name), self._store["offsets"]
+        host = buf.detach().cpu()
+        for w, v in zip([w for w in self.weight_specs if w.trainable], arrays):
+            a = offs[id(w)]
+            host[a:a + w.size] = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
+        buf.copy_(host)
 
     def run_train_step(self, plan):
         """Forward, backward and optimizer step on buffers already resident in HBM (no host sync)."""

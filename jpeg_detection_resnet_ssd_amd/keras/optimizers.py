@@ -1,16 +1,155 @@
-"""keras.optimizers.SGD with the Keras 2.2.4 update rule (differs from torch.optim.SGD whenever the
-learning rate changes): lr_t = lr / (1 + decay * iterations); v = momentum*v - lr_t*g;
-p += v  (or p += momentum*v - lr_t*g with nesterov=True).
+"""keras.optimizers.SGD, Adam (with amsgrad) and Adadelta with the Keras 2.2.4 update rules.
+
+SGD (differs from torch.optim.SGD whenever the learning rate changes): lr_t = lr / (1 + decay * iterations);
+v = momentum*v - lr_t*g; p += v  (or p += momentum*v - lr_t*g with nesterov=True).
 Call sites: localisation_part/training_dct_pascal_j2d_resnet.py:152,
-classification_part/config/resnet/config_file.py:58-63."""
+classification_part/config/resnet/config_file.py:58-63.
+
+Adam and Adadelta.  Call sites: localisation_part/evaluation.py:102 and inference.py:104 (Adam(lr=0.001, beta_1=0.9,
+beta_2=0.999, epsilon=1e-08, decay=0.0)); classification_part/template_keras/config/template_config.py (Adadelta).  Keras is
+not a dependency: `adam_host` and `adadelta_host` below are the statement of both rules, in numpy, and csrc/dj_optim.hip
+equals them bit for bit.  All tensor arithmetic is float32; every product, sum, quotient and square root is rounded once,
+in the order written (fl); nothing is fused.  Both share the head of the SGD kernel, the effective gradient
+
+    g' = fl( fl(g * grad_scale) + fl( fl32(2*l2) * p ) )
+
+where grad_scale is the data-parallel 1/world and l2 the segment's kernel_regularizer (in Keras the penalty is part of the
+loss, so it enters the moments; 0 for un-regularised segments -- a product all the same, so p = Inf gives NaN).
+
+Adam (Keras holds the betas as float32 variables, so 1 - beta is a float32 subtraction):
+
+    omb1 = fl32(1) - fl32(beta_1);  omb2 = fl32(1) - fl32(beta_2)
+    m  = fl(fl(b1 * m) + fl(omb1 * g'))
+    v  = fl(fl(b2 * v) + fl(omb2 * fl(g' * g')))
+    amsgrad:  vhat = max(vhat, v)  (np.maximum: NaN in either gives NaN);  d = vhat     else  d = v
+    p  = fl(p - fl( fl(lr_t * m) / fl(sqrt(d) + eps) ))
+
+with, in Python float64 and rounded once to float32 by the caller,
+
+    lr_dec = lr / (1 + decay * iterations) if decay > 0 else lr          (Adam.current_lr())
+    t = iterations + 1
+    lr_t = lr_dec * sqrt(1 - beta_2**t) / (1 - beta_1**t)                (Adam.step_size())
+
+Adadelta (rho is a Python float in Keras: 1 - rho is subtracted in float64 and rounded once):
+
+    omr = fl32(1.0 - rho)
+    a   = fl(fl(rho * a) + fl(omr * fl(g' * g')))
+    u   = fl( fl(g' * fl(sqrt(fl(d + eps)))) / fl(sqrt(fl(a + eps))) )
+    p   = fl(p - fl(lr_dec * u))
+    d   = fl(fl(rho * d) + fl(omr * fl(u * u)))
+
+epsilon=None means K.epsilon() = 1e-7.  clipnorm / clipvalue are not implemented and raise.  Model.compile takes the
+three classes as instances; by name only 'sgd', as before (see `get`).
+
+Optimizer state.  `get_weights()` / `set_weights()` work once the optimizer is compiled into a model, and return / accept
+numpy arrays in Keras' order, the per-weight arrays in the order of the model's trainable weights and shaped like them:
+SGD [iterations] + moments;  Adam [iterations] + ms + vs + vhats;  Adadelta [iterations] + accumulators + delta_accumulators.
+`iterations` is an int64 scalar.  Without amsgrad Keras 2.2.4 keeps every vhat as one zeros(1): so does this list, so that
+its length is what a Keras user expects; set_weights checks those entries' shape and otherwise ignores them."""
+import math
+import weakref
+
+import numpy as np
+
+EPSILON = 1e-7      # K.epsilon()
+
+
+def _f32(x):
+    return np.float32(x)
+
+
+def effective_gradient_host(p, g, l2, grad_scale):
+    """g' of the module docstring, float32."""
+    p, g = np.asarray(p, np.float32), np.asarray(g, np.float32)
+    with np.errstate(all="ignore"):
+        return g * _f32(grad_scale) + (_f32(2.0) * _f32(l2)) * p
+
+
+def adam_host(p, g, m, v, vhat, lr_t, beta_1, beta_2, epsilon, l2, grad_scale):
+    """One Adam step as the module docstring states it -> (p, m, v, vhat); vhat None = no amsgrad (None is returned)."""
+    p, m, v = (np.asarray(t, np.float32) for t in (p, m, v))
+    b1, b2, one = _f32(beta_1), _f32(beta_2), _f32(1.0)
+    omb1, omb2 = one - b1, one - b2
+    with np.errstate(all="ignore"):
+        ge = effective_gradient_host(p, g, l2, grad_scale)
+        m = b1 * m + omb1 * ge
+        v = b2 * v + omb2 * (ge * ge)
+        if vhat is not None:
+            vhat = np.maximum(np.asarray(vhat, np.float32), v)
+            d = vhat
+        else:
+            d = v
+        p = p - (_f32(lr_t) * m) / (np.sqrt(d) + _f32(epsilon))
+    assert p.dtype == m.dtype == v.dtype == np.float32
+    return p, m, v, vhat
+
+
+def adadelta_host(p, g, a, d, lr_dec, rho, epsilon, l2, grad_scale):
+    """One Adadelta step as the module docstring states it -> (p, accumulator, delta_accumulator)."""
+    p, a, d = (np.asarray(t, np.float32) for t in (p, a, d))
+    omr, rho, eps = _f32(1.0 - float(rho)), _f32(rho), _f32(epsilon)
+    with np.errstate(all="ignore"):
+        ge = effective_gradient_host(p, g, l2, grad_scale)
+        a = rho * a + omr * (ge * ge)
+        u = (ge * np.sqrt(d + eps)) / np.sqrt(a + eps)
+        p = p - _f32(lr_dec) * u
+        d = rho * d + omr * (u * u)
+    assert p.dtype == a.dtype == d.dtype == np.float32
+    return p, a, d
+
+
+def _check_kwargs(kwargs, strict):
+    for k in kwargs:
+        if k in ("clipnorm", "clipvalue"):
+            raise NotImplementedError("%s is not implemented: no gradient clipping runs on the update kernels" % k)
+        if strict:
+            raise TypeError("Unexpected keyword argument passed to optimizer: " + str(k))
 
 
 class Optimizer(object):
-    pass
+    state_names = ()        # the per-weight state lists of get_weights(), in Keras' order
+
+    def _bind(self, model):
+        self._model = weakref.ref(model)
+
+    def _bound_model(self):
+        model = getattr(self, "_model", lambda: None)()
+        if model is None or model.optimizer is not self:
+            raise RuntimeError("the optimizer's weights exist once it is compiled into a model: model.compile(optimizer, ...)")
+        return model
+
+    def get_weights(self):
+        """[iterations] + the state lists (see the module docstring), as numpy arrays."""
+        model = self._bound_model()
+        out = [np.asarray(self.iterations, dtype=np.int64)]
+        for name in self.state_names:
+            out.extend(model._optimizer_state_arrays(name))
+        return out
+
+    def set_weights(self, weights):
+        model = self._bound_model()
+        want = [()] + [s for name in self.state_names for s in model._optimizer_state_shapes(name)]
+        if len(want) != len(weights):
+            raise ValueError("Length of the specified weight list (" + str(len(weights)) + ") does not match the number of "
+                             "weights of the optimizer (" + str(len(want)) + ")")
+        weights = [np.asarray(w) for w in weights]
+        for pv, w in zip(want, weights):
+            if tuple(pv) != tuple(w.shape):
+                raise ValueError("Optimizer weight shape " + str(tuple(pv)) + " not compatible with provided weight shape "
+                                 + str(tuple(w.shape)))
+        self.iterations = int(weights[0])
+        i = 1
+        for name in self.state_names:
+            k = len(model._optimizer_state_shapes(name))
+            model._set_optimizer_state_arrays(name, weights[i:i + k])
+            i += k
 
 
 class SGD(Optimizer):
+    state_names = ("moments",)
+
     def __init__(self, lr=0.01, momentum=0.0, decay=0.0, nesterov=False, **kwargs):
+        _check_kwargs(kwargs, strict=False)
         self.lr = float(lr)
         self.momentum = float(momentum)
         self.decay = float(decay)
@@ -26,3 +165,67 @@ class SGD(Optimizer):
 
     def get_config(self):
         return {"lr": self.lr, "momentum": self.momentum, "decay": self.decay, "nesterov": self.nesterov}
+
+
+class Adam(Optimizer):
+    state_names = ("ms", "vs", "vhats")
+
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0., amsgrad=False, **kwargs):
+        _check_kwargs(kwargs, strict=True)
+        self.lr = float(lr)
+        self.beta_1 = float(beta_1)
+        self.beta_2 = float(beta_2)
+        self.epsilon = EPSILON if epsilon is None else float(epsilon)
+        self.decay = float(decay)
+        self.initial_decay = float(decay)
+        self.amsgrad = bool(amsgrad)
+        self.iterations = 0
+
+    def current_lr(self):
+        lr = self.lr
+        if self.initial_decay > 0:
+            lr = lr / (1.0 + self.decay * self.iterations)
+        return lr
+
+    def step_size(self):
+        """lr_t of the next step, in float64; the kernel takes it rounded once to float32."""
+        t = self.iterations + 1
+        return self.current_lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+
+    def get_config(self):
+        return {"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay, "epsilon": self.epsilon,
+                "amsgrad": self.amsgrad}
+
+
+class Adadelta(Optimizer):
+    state_names = ("accumulators", "delta_accumulators")
+
+    def __init__(self, lr=1.0, rho=0.95, epsilon=None, decay=0., **kwargs):
+        _check_kwargs(kwargs, strict=True)
+        self.lr = float(lr)
+        self.rho = float(rho)
+        self.epsilon = EPSILON if epsilon is None else float(epsilon)
+        self.decay = float(decay)
+        self.initial_decay = float(decay)
+        self.iterations = 0
+
+    def current_lr(self):
+        lr = self.lr
+        if self.initial_decay > 0:
+            lr = lr / (1.0 + self.decay * self.iterations)
+        return lr
+
+    def get_config(self):
+        return {"lr": self.lr, "rho": self.rho, "decay": self.decay, "epsilon": self.epsilon}
+
+
+def get(identifier):
+    """What Model.compile takes: an instance of SGD, Adam or Adadelta, or the name 'sgd' (case-insensitive).  Adam and
+    Adadelta are NOT resolved by name: compile(optimizer="adam") has always raised NotImplementedError here and code may
+    rely on it (tests/test_callbacks_cpu.py does), so the two new optimizers are passed as instances."""
+    if isinstance(identifier, str) and identifier.lower() == "sgd":
+        return SGD()
+    if isinstance(identifier, (SGD, Adam, Adadelta)):
+        return identifier
+    raise NotImplementedError("optimizer %r: pass an instance of keras.optimizers.SGD, Adam or Adadelta (the three with an "
+                              "update kernel), or the name 'sgd'" % (identifier,))

@@ -399,17 +399,17 @@ int dj_ssd_loss_bwd(const float* y_true, const float* y_pred, long nbox, int n_c
 int dj_categorical_crossentropy(const float* y_true, const float* probs, long rows, int C, float upstream,
                                 float* loss_rows, float* d_probs, float* out_mean, void* stream);
 
-/* ---- keras.optimizers.SGD.get_updates (L/training_dct_pascal_j2d_resnet.py:152;
- * C/config/resnet/config_file.py:58-63) with the l2 kernel_regularizer gradient (2*l2*w) and the
- * data-parallel 1/world_size folded in.  lr_t = lr / (1 + decay * iterations) is computed by the caller. */
-int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, long n, float lr_t, float momentum,
-                           int nesterov, float l2, float grad_scale, float* sumsq, void* stream);
-
-/* ---- keras.optimizers.Adam.get_updates and Adadelta.get_updates (Keras 2.2.4; L/evaluation.py:102, L/inference.py:104 build
+/* ---- keras.optimizers.SGD.get_updates (L/training_dct_pascal_j2d_resnet.py:152; C/config/resnet/config_file.py:58-63),
+ * Adam.get_updates and Adadelta.get_updates (Keras 2.2.4; L/evaluation.py:102, L/inference.py:104 build
  * Adam(lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-08, decay=0.0); C/template_keras/config/template_config.py imports
- * Adadelta).  keras/optimizers.py states both in numpy (adam_host, adadelta_host); the entry points equal that statement
- * bit for bit: fp32 throughout, every operation rounded once in the order written, no fma.  Both share the head of
- * dj_sgd_momentum_update, the l2 kernel_regularizer gradient and the data-parallel 1/world_size:
+ * Adadelta), each with the l2 kernel_regularizer gradient (2*l2*p) and the data-parallel 1/world_size folded in.
+ * keras/optimizers.py states the three in numpy (sgd_host, adam_host, adadelta_host); the entry points equal that
+ * statement bit for bit: fp32 throughout, every operation rounded once in the order written, and no fma but the two that
+ * the SGD statement writes.
+ * dj_sgd_momentum_update:  g' = fma(g, grad_scale, (l2 + l2) * p);   v = momentum * v - lr_t * g'
+ *                      p = nesterov ? fma(momentum, v, p) - lr_t * g' : p + v
+ *   with lr_t = lr / (1 + decay * iterations) computed by the caller.
+ * Adam and Adadelta round both products of their effective gradient:
  *     g' = g * grad_scale + (2 * l2) * p
  * dj_adam_update:      m = beta_1 * m + (1 - beta_1) * g';   v = beta_2 * v + (1 - beta_2) * (g' * g')
  *                      vhat != NULL (amsgrad): vhat = max(vhat, v), a NaN on either side giving NaN, and d = vhat; else d = v
@@ -420,11 +420,13 @@ int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, lon
  *                      p = p - lr * u;   d = rho * d + one_minus_rho * (u * u)
  *   with lr = lr / (1 + decay * iterations) and one_minus_rho = (float)(1.0 - rho), subtracted in double as Keras does with
  *   its Python float, both computed by the caller.
- * sumsq != NULL: sumsq[0] += sum(p^2) before the update, as dj_sgd_momentum_update reports it.  One thread per four
+ * All three.  sumsq != NULL: sumsq[0] += sum(p^2) before the update, in one fp32 addition.  One thread per four
  * consecutive elements in a grid-stride loop of at most dj_optim_groups_per_pass() threads; 16-byte accesses when every
  * pointer is 16-byte aligned, element by element otherwise.  DJ_ERR_ARG for a null pointer (vhat and sumsq excepted),
  * n <= 0, or buffers that overlap. ---- */
 long dj_optim_groups_per_pass(void);
+int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, long n, float lr_t, float momentum,
+                           int nesterov, float l2, float grad_scale, float* sumsq /* may be NULL */, void* stream);
 int dj_adam_update(float* param, const float* grad, float* m, float* v, float* vhat /* NULL: no amsgrad */, long n,
                    float lr_t, float beta_1, float beta_2, float epsilon, float l2, float grad_scale,
                    float* sumsq /* may be NULL */, void* stream);

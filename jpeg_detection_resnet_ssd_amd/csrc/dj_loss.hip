@@ -1,12 +1,10 @@
 // Softmax, the SSD multibox loss with batch-wide hard-negative mining, categorical
-// cross-entropy and the Keras-formula SGD update.
+// cross-entropy and global average pooling.
 // Reference: localisation_part/keras_loss_function/keras_ssd_loss.py:53-211 (SSDLoss),
 // localisation_part/models/keras_ssd300_dct_j2d_resnet.py:873 (softmax),
-// localisation_part/training_dct_pascal_j2d_resnet.py:152 and
-// classification_part/config/resnet/config_file.py:58-65 (SGD, categorical_crossentropy).
+// classification_part/config/resnet/config_file.py:58-65 (categorical_crossentropy).
 #include "../../include/dj_hip.h"
 #include "dj_common.h"
-#include <atomic>
 
 static inline int ew_blocks(long total) {
   long b = (total + 255) / 256;
@@ -484,78 +482,6 @@ extern "C" int dj_categorical_crossentropy(const float* y_true, const float* pro
   DJ_CHECK_LAUNCH("dj_cce");
   hipLaunchKernelGGL(dj_mean_kernel, dim3(1), dim3(256), 0, s, loss_rows, rows, out_mean);
   DJ_CHECK_LAUNCH("dj_mean");
-  return DJ_OK;
-}
-
-// ---------------------------------------------------------------------------------
-// keras.optimizers.SGD:  g' = g*grad_scale + 2*l2*p ; v = momentum*v - lr_t*g' ;
-//                        p += nesterov ? momentum*v - lr_t*g' : v
-// Optionally accumulates sum(p^2) (pre-update) into sumsq[0] for the l2 penalty report.  The workgroups add their sums in
-// fp64 to an accumulator of the library and take a ticket; the one that takes the last adds the total to sumsq[0], in ONE
-// fp32 addition, and clears both (the ticket scheme of the BatchNormalization statistics in dj_igemm.h).  An fp32 atomic per
-// workgroup on sumsq[0] itself rounded the running total up to 4096 times: 0.7e-6 .. 2e-6 of the sum at a million elements,
-// different from run to run.  Launches that may be in flight together must not share an accumulator: the launcher hands
-// out DJ_SGD_SLOTS of them in turn.  The workgroups spread their sums over DJ_SGD_REPLICAS copies, each on a 128-byte line
-// of its own like the ticket, so that no line takes more atomics than sumsq[0] took.
-// ---------------------------------------------------------------------------------
-#define DJ_SGD_SLOTS 64
-#define DJ_SGD_REPLICAS 8
-struct DjSgdSlot {
-  struct {
-    double v;
-    double pad[15];
-  } acc[DJ_SGD_REPLICAS];
-  unsigned ticket;
-  unsigned pad[31];
-};
-__device__ DjSgdSlot dj_sgd_slots[DJ_SGD_SLOTS];
-
-__global__ __launch_bounds__(256) void dj_sgd_kernel(float* p, const float* g, float* v, long n, float lr_t,
-                                                      float momentum, int nesterov, float l2, float grad_scale,
-                                                      float* sumsq, int slot) {
-  float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    float gi = g[i] * grad_scale + 2.f * l2 * pi;
-    float vi = momentum * v[i] - lr_t * gi;
-    v[i] = vi;
-    p[i] = nesterov ? pi + momentum * vi - lr_t * gi : pi + vi;
-    acc += pi * pi;
-  }
-  if (sumsq) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      DjSgdSlot* s = &dj_sgd_slots[slot];
-      atomicAdd(&s->acc[blockIdx.x % DJ_SGD_REPLICAS].v,
-                ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]));
-      // the ticket after the sum has been performed: device-scope atomics are complete when vmcnt reaches zero
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (atomicAdd(&s->ticket, 1u) == gridDim.x - 1u) {
-        double total = 0.0;
-        for (int r = 0; r < DJ_SGD_REPLICAS; ++r) {
-          total += __hip_atomic_load(&s->acc[r].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&s->acc[r].v, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __hip_atomic_store(&s->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        atomicAdd(sumsq, (float)total);
-      }
-    }
-  }
-}
-
-extern "C" int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, long n, float lr_t,
-                                      float momentum, int nesterov, float l2, float grad_scale, float* sumsq,
-                                      void* stream) {
-  DJ_CHECK_ARG(param && grad && velocity && n > 0, "sgd: bad arguments");
-  static std::atomic<unsigned> next_slot{0};
-  const int slot = sumsq ? (int)(next_slot.fetch_add(1u) % DJ_SGD_SLOTS) : 0;
-  hipLaunchKernelGGL(dj_sgd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, param, grad, velocity, n,
-                     lr_t, momentum, nesterov, l2, grad_scale, sumsq, slot);
-  DJ_CHECK_LAUNCH("dj_sgd_momentum_update");
   return DJ_OK;
 }
 

@@ -1,15 +1,24 @@
-// keras.optimizers.Adam (with amsgrad) and Adadelta: one memory-bound pass over a segment of the flat parameter buffer,
-// equal bit for bit to adam_host / adadelta_host of keras/optimizers.py (the host statement).  All arithmetic is fp32,
-// every product, sum, quotient and square root rounded once in the order the statement writes them: nothing may be
-// contracted into an fma, hence the pragma; the division and sqrtf are hipcc's correctly rounded expansions.
+// keras.optimizers.SGD, Adam (with amsgrad) and Adadelta: one memory-bound pass over a segment of the flat parameter
+// buffer, equal bit for bit to sgd_host / adam_host / adadelta_host of keras/optimizers.py (the host statement).  All
+// arithmetic is fp32, every product, sum, quotient and square root rounded once in the order the statement writes them:
+// nothing is contracted into an fma, hence the pragma, and the fmas of the SGD statement are written out as
+// __builtin_fmaf; the division and sqrtf are hipcc's correctly rounded expansions.
 //
-// One thread per group of four consecutive elements in a grid-stride loop over at most DJ_OPTIM_MAX_BLOCKS workgroups of
-// 256 threads.  VEC4: every pointer is 16-byte aligned, so whole groups move as 16-byte loads and stores; the last,
-// partial group and every group of an unaligned launch go element by element.  Every stream is read once and written
-// once per step and a segment of a real model is far larger than the L2, so the gradient and the state buffers move with
-// non-temporal loads and stores; the parameters, which the next forward pass reads, keep the default policy.
+// A rule is a struct of its state pointers, its scalars and the update of one element.  Everything else exists once, in
+// dj_optim_kernel and optim_launch.  One thread per group of four consecutive elements in a grid-stride loop over at most
+// DJ_OPTIM_MAX_BLOCKS workgroups of 256 threads.  VEC4: every pointer is 16-byte aligned, so whole groups move as 16-byte
+// loads and stores; the last, partial group and every group of an unaligned launch go element by element.  Every stream
+// is read once and written once per step and a segment of a real model is far larger than the L2, so the gradient and the
+// state buffers move with non-temporal loads and stores; the parameters, which the next forward pass reads, keep the
+// default policy.  sumsq != NULL: sum(p^2) of the pre-update parameters goes through dj_sumsq_finish; the slots are
+// shared by the three rules.
+//
+// SGD used to be a kernel of its own in dj_loss.hip (one element per thread, 4096 workgroups, default cache policy, null
+// checks only).  As a rule of this file it gained the four-per-thread geometry, so that dj_optim_groups_per_pass()
+// describes it too, the non-temporal gradient and velocity streams, and the refusal of overlapping buffers.
 #pragma clang fp contract(off)
 #include <atomic>
+#include <cstdio>
 
 #include "../../include/dj_hip.h"
 #include "dj_common.h"
@@ -42,6 +51,27 @@ __device__ __forceinline__ void st_stream(float* p, f32x4 v) {
 #endif
 }
 
+// ---- the rules: NS state buffers, their names for the error texts, and element(p, g, s[NS]) ------------------------------
+
+// t = (2*l2)*p ; g' = fma(g, grad_scale, t) ; v = momentum*v - lr_t*g' ; p = nesterov ? fma(momentum, v, p) - lr_t*g' : p + v
+// -- what hipcc made of the plain expressions while it was free to contract them; the select is wave-uniform
+struct DjSgdRule {
+  static constexpr int NS = 1;
+  static constexpr const char* NAME = "dj_sgd_momentum_update";
+  static constexpr const char* BUFFERS = "param, grad and velocity";
+  static constexpr const char* STATE[NS] = {"velocity"};
+  float* state[NS];
+  float lr_t, momentum, l2x2, grad_scale;
+  int nesterov;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = __builtin_fmaf(g, grad_scale, l2x2 * p);
+    const float step = lr_t * ge;
+    const float v = momentum * s[0] - step;
+    s[0] = v;
+    p = nesterov ? __builtin_fmaf(momentum, v, p) - step : p + v;
+  }
+};
+
 struct DjAdamScalars {
   float lr_t, b1, b2, omb1, omb2, eps, l2x2, grad_scale;
 };
@@ -50,80 +80,46 @@ struct DjAdamScalars {
 __device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
 
 template <bool AMSGRAD>
-__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float& vh, const DjAdamScalars& k,
-                                             float& acc) {
-  acc += p * p;
-  const float ge = g * k.grad_scale + k.l2x2 * p;
-  m = k.b1 * m + k.omb1 * ge;
-  v = k.b2 * v + k.omb2 * (ge * ge);
-  float d = v;
-  if (AMSGRAD) {
-    vh = max_nan(vh, v);
-    d = vh;
-  }
-  p = p - (k.lr_t * m) / (sqrtf(d) + k.eps);
-}
-
-template <bool AMSGRAD, bool VEC4>
-__global__ __launch_bounds__(256) void dj_adam_kernel(float* p, const float* g, float* m, float* v, float* vhat, long n,
-                                                       DjAdamScalars k, float* sumsq, int slot) {
-  float acc = 0.f;
-  const long groups = (n + 3) >> 2;
-  for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (long)gridDim.x * blockDim.x) {
-    const long i0 = gi << 2;
-    if (VEC4 && i0 + 4 <= n) {
-      f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
-      const f32x4 gv = ld_stream(g + i0);
-      f32x4 mv = ld_stream(m + i0), vv = ld_stream(v + i0), hv = {0.f, 0.f, 0.f, 0.f};
-      if (AMSGRAD) hv = ld_stream(vhat + i0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pv[e], me = mv[e], ve = vv[e], he = hv[e];
-        adam_element<AMSGRAD>(pe, gv[e], me, ve, he, k, acc);
-        pv[e] = pe;
-        mv[e] = me;
-        vv[e] = ve;
-        hv[e] = he;
-      }
-      *reinterpret_cast<f32x4*>(p + i0) = pv;
-      st_stream(m + i0, mv);
-      st_stream(v + i0, vv);
-      if (AMSGRAD) st_stream(vhat + i0, hv);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const long i = i0 + e;
-        if (i < n) {
-          float pi = p[i], mi = m[i], vi = v[i], hi = AMSGRAD ? vhat[i] : 0.f;
-          adam_element<AMSGRAD>(pi, g[i], mi, vi, hi, k, acc);
-          p[i] = pi;
-          m[i] = mi;
-          v[i] = vi;
-          if (AMSGRAD) vhat[i] = hi;
-        }
-      }
+struct DjAdamRule {
+  static constexpr int NS = AMSGRAD ? 3 : 2;
+  static constexpr const char* NAME = "dj_adam_update";
+  static constexpr const char* BUFFERS = "param, grad, m, v and vhat";
+  static constexpr const char* STATE[3] = {"m", "v", "vhat"};
+  float* state[NS];
+  DjAdamScalars k;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * k.grad_scale + k.l2x2 * p;
+    s[0] = k.b1 * s[0] + k.omb1 * ge;
+    s[1] = k.b2 * s[1] + k.omb2 * (ge * ge);
+    float d = s[1];
+    if (AMSGRAD) {
+      s[NS - 1] = max_nan(s[NS - 1], s[1]);
+      d = s[NS - 1];
     }
+    p = p - (k.lr_t * s[0]) / (sqrtf(d) + k.eps);
   }
-  if (sumsq) dj_sumsq_finish(acc, &dj_optim_slots[slot], sumsq);
-}
-
-struct DjAdadeltaScalars {
-  float lr, rho, omr, eps, l2x2, grad_scale;
 };
 
-__device__ __forceinline__ void adadelta_element(float& p, float g, float& a, float& d, const DjAdadeltaScalars& k,
-                                                 float& acc) {
-  acc += p * p;
-  const float ge = g * k.grad_scale + k.l2x2 * p;
-  a = k.rho * a + k.omr * (ge * ge);
-  const float u = (ge * sqrtf(d + k.eps)) / sqrtf(a + k.eps);
-  p = p - k.lr * u;
-  d = k.rho * d + k.omr * (u * u);
-}
+struct DjAdadeltaRule {
+  static constexpr int NS = 2;
+  static constexpr const char* NAME = "dj_adadelta_update";
+  static constexpr const char* BUFFERS = "param, grad, accum and delta_accum";
+  static constexpr const char* STATE[NS] = {"accum", "delta_accum"};
+  float* state[NS];
+  float lr, rho, omr, eps, l2x2, grad_scale;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * grad_scale + l2x2 * p;
+    s[0] = rho * s[0] + omr * (ge * ge);
+    const float u = (ge * sqrtf(s[1] + eps)) / sqrtf(s[0] + eps);
+    p = p - lr * u;
+    s[1] = rho * s[1] + omr * (u * u);
+  }
+};
 
-template <bool VEC4>
-__global__ __launch_bounds__(256) void dj_adadelta_kernel(float* p, const float* g, float* a, float* d, long n,
-                                                           DjAdadeltaScalars k, float* sumsq, int slot) {
+// ---- the pass ----------------------------------------------------------------------------------------------------------
+template <class Rule, bool VEC4>
+__global__ __launch_bounds__(256) void dj_optim_kernel(float* p, const float* g, long n, Rule r, float* sumsq, int slot) {
+  constexpr int NS = Rule::NS;
   float acc = 0.f;
   const long groups = (n + 3) >> 2;
   for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (long)gridDim.x * blockDim.x) {
@@ -131,28 +127,36 @@ __global__ __launch_bounds__(256) void dj_adadelta_kernel(float* p, const float*
     if (VEC4 && i0 + 4 <= n) {
       f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
       const f32x4 gv = ld_stream(g + i0);
-      f32x4 av = ld_stream(a + i0), dv = ld_stream(d + i0);
+      f32x4 sv[NS];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) sv[k] = ld_stream(r.state[k] + i0);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float pe = pv[e], ae = av[e], de = dv[e];
-        adadelta_element(pe, gv[e], ae, de, k, acc);
+        float pe = pv[e], se[NS];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) se[k] = sv[k][e];
+        acc += pe * pe;
+        r.element(pe, gv[e], se);
         pv[e] = pe;
-        av[e] = ae;
-        dv[e] = de;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sv[k][e] = se[k];
       }
       *reinterpret_cast<f32x4*>(p + i0) = pv;
-      st_stream(a + i0, av);
-      st_stream(d + i0, dv);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) st_stream(r.state[k] + i0, sv[k]);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const long i = i0 + e;
         if (i < n) {
-          float pi = p[i], ai = a[i], di = d[i];
-          adadelta_element(pi, g[i], ai, di, k, acc);
+          float pi = p[i], si[NS];
+#pragma unroll
+          for (int k = 0; k < NS; ++k) si[k] = r.state[k][i];
+          acc += pi * pi;
+          r.element(pi, g[i], si);
           p[i] = pi;
-          a[i] = ai;
-          d[i] = di;
+#pragma unroll
+          for (int k = 0; k < NS; ++k) r.state[k][i] = si[k];
         }
       }
     }
@@ -160,65 +164,63 @@ __global__ __launch_bounds__(256) void dj_adadelta_kernel(float* p, const float*
   if (sumsq) dj_sumsq_finish(acc, &dj_optim_slots[slot], sumsq);
 }
 
-static inline bool overlaps(const float* a, const float* b, long n) {
-  return a && b && a < b + n && b < a + n;
-}
+static inline bool overlaps(const float* a, const float* b, long n) { return a < b + n && b < a + n; }
 
 static int next_slot(const float* sumsq) {
   static std::atomic<unsigned> next{0};
   return sumsq ? (int)(next.fetch_add(1u) % DJ_SUMSQ_SLOTS) : 0;
 }
 
+// The checks and the launch of every rule: no null pointer and n > 0; no two of param, grad and the state buffers
+// overlap; the 16-byte path only if every one of them is 16-byte aligned.
+template <class Rule>
+static int optim_launch(float* param, const float* grad, long n, const Rule& r, float* sumsq, void* stream) {
+  const float* buf[2 + Rule::NS] = {param, grad};
+  bool present = param && grad;
+  char list[160];
+  int len = snprintf(list, sizeof list, "param %p, grad %p", (void*)param, (const void*)grad);
+  for (int k = 0; k < Rule::NS; ++k) {
+    buf[2 + k] = r.state[k];
+    present = present && r.state[k];
+    len += snprintf(list + len, sizeof list - len, ", %s %p", Rule::STATE[k], (void*)r.state[k]);
+  }
+  DJ_CHECK_ARG(present && n > 0, "%s: bad arguments (%s, n %ld)", Rule::NAME, list, n);
+  uintptr_t bits = 0;
+  for (int a = 0; a < 2 + Rule::NS; ++a) {
+    bits |= (uintptr_t)buf[a];
+    for (int b = a + 1; b < 2 + Rule::NS; ++b)
+      DJ_CHECK_ARG(!overlaps(buf[a], buf[b], n), "%s: %s must not overlap", Rule::NAME, Rule::BUFFERS);
+  }
+  const dim3 grid(optim_blocks((n + 3) >> 2)), block(256);
+  const int slot = next_slot(sumsq);
+  if ((bits & 15) == 0)
+    hipLaunchKernelGGL((dj_optim_kernel<Rule, true>), grid, block, 0, (hipStream_t)stream, param, grad, n, r, sumsq, slot);
+  else
+    hipLaunchKernelGGL((dj_optim_kernel<Rule, false>), grid, block, 0, (hipStream_t)stream, param, grad, n, r, sumsq, slot);
+  DJ_CHECK_LAUNCH(Rule::NAME);
+  return DJ_OK;
+}
+
 extern "C" long dj_optim_groups_per_pass(void) { return (long)DJ_OPTIM_MAX_BLOCKS * 256; }
+
+extern "C" int dj_sgd_momentum_update(float* param, const float* grad, float* velocity, long n, float lr_t,
+                                      float momentum, int nesterov, float l2, float grad_scale, float* sumsq,
+                                      void* stream) {
+  return optim_launch(param, grad, n, DjSgdRule{{velocity}, lr_t, momentum, l2 + l2, grad_scale, nesterov}, sumsq, stream);
+}
 
 extern "C" int dj_adam_update(float* param, const float* grad, float* m, float* v, float* vhat, long n, float lr_t,
                               float beta_1, float beta_2, float epsilon, float l2, float grad_scale, float* sumsq,
                               void* stream) {
-  DJ_CHECK_ARG(param && grad && m && v && n > 0, "dj_adam_update: bad arguments (param %p, grad %p, m %p, v %p, n %ld)",
-               (void*)param, (const void*)grad, (void*)m, (void*)v, n);
-  DJ_CHECK_ARG(!overlaps(param, m, n) && !overlaps(param, v, n) && !overlaps(param, vhat, n) && !overlaps(m, v, n) &&
-                   !overlaps(m, vhat, n) && !overlaps(v, vhat, n) && !overlaps(param, grad, n),
-               "dj_adam_update: param, grad, m, v and vhat must not overlap");
   const DjAdamScalars k = {lr_t, beta_1, beta_2, 1.f - beta_1, 1.f - beta_2, epsilon, 2.f * l2, grad_scale};
-  const long groups = (n + 3) >> 2;
-  const bool v4 = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)vhat) & 15) == 0;
-  const dim3 grid(optim_blocks(groups)), block(256);
-  const int slot = next_slot(sumsq);
-  hipStream_t s = (hipStream_t)stream;
-  if (vhat) {
-    if (v4)
-      hipLaunchKernelGGL((dj_adam_kernel<true, true>), grid, block, 0, s, param, grad, m, v, vhat, n, k, sumsq, slot);
-    else
-      hipLaunchKernelGGL((dj_adam_kernel<true, false>), grid, block, 0, s, param, grad, m, v, vhat, n, k, sumsq, slot);
-  } else {
-    if (v4)
-      hipLaunchKernelGGL((dj_adam_kernel<false, true>), grid, block, 0, s, param, grad, m, v, vhat, n, k, sumsq, slot);
-    else
-      hipLaunchKernelGGL((dj_adam_kernel<false, false>), grid, block, 0, s, param, grad, m, v, vhat, n, k, sumsq, slot);
-  }
-  DJ_CHECK_LAUNCH("dj_adam_update");
-  return DJ_OK;
+  if (vhat) return optim_launch(param, grad, n, DjAdamRule<true>{{m, v, vhat}, k}, sumsq, stream);
+  return optim_launch(param, grad, n, DjAdamRule<false>{{m, v}, k}, sumsq, stream);
 }
 
 extern "C" int dj_adadelta_update(float* param, const float* grad, float* accum, float* delta_accum, long n, float lr,
                                   float rho, float one_minus_rho, float epsilon, float l2, float grad_scale,
                                   float* sumsq, void* stream) {
-  DJ_CHECK_ARG(param && grad && accum && delta_accum && n > 0,
-               "dj_adadelta_update: bad arguments (param %p, grad %p, accum %p, delta_accum %p, n %ld)", (void*)param,
-               (const void*)grad, (void*)accum, (void*)delta_accum, n);
-  DJ_CHECK_ARG(!overlaps(param, accum, n) && !overlaps(param, delta_accum, n) && !overlaps(accum, delta_accum, n) &&
-                   !overlaps(param, grad, n),
-               "dj_adadelta_update: param, grad, accum and delta_accum must not overlap");
-  const DjAdadeltaScalars k = {lr, rho, one_minus_rho, epsilon, 2.f * l2, grad_scale};
-  const long groups = (n + 3) >> 2;
-  const bool v4 = (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)accum | (uintptr_t)delta_accum) & 15) == 0;
-  const dim3 grid(optim_blocks(groups)), block(256);
-  const int slot = next_slot(sumsq);
-  hipStream_t s = (hipStream_t)stream;
-  if (v4)
-    hipLaunchKernelGGL((dj_adadelta_kernel<true>), grid, block, 0, s, param, grad, accum, delta_accum, n, k, sumsq, slot);
-  else
-    hipLaunchKernelGGL((dj_adadelta_kernel<false>), grid, block, 0, s, param, grad, accum, delta_accum, n, k, sumsq, slot);
-  DJ_CHECK_LAUNCH("dj_adadelta_update");
-  return DJ_OK;
+  return optim_launch(param, grad, n,
+                      DjAdadeltaRule{{accum, delta_accum}, lr, rho, one_minus_rho, epsilon, 2.f * l2, grad_scale}, sumsq,
+                      stream);
 }

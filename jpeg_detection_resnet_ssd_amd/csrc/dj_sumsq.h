@@ -1,9 +1,11 @@
 // Sum of one fp32 value per thread over a whole launch of 256-thread workgroups, added to a device float in ONE fp32
-// addition (the scheme dj_sgd_kernel in dj_loss.hip describes, and the ticket scheme of the BatchNormalization statistics
-// in dj_igemm.h): wave shuffle in fp32, the four wave sums of a workgroup in fp64 into one of DJ_SUMSQ_REPLICAS accumulators
-// of a slot, a ticket, and the workgroup that takes the last ticket adds the fp64 total to out[0] and clears the slot.
-// Every accumulator and the ticket sit on a 128-byte line of their own.  Launches that may be in flight together must
-// not share a slot: the launcher hands them out in turn.
+// addition (the ticket scheme of the BatchNormalization statistics in dj_igemm.h): wave shuffle in fp32, the four wave sums
+// of a workgroup in fp64 into one of DJ_SUMSQ_REPLICAS accumulators of a slot, a ticket, and the workgroup that takes the
+// last ticket adds the fp64 total to out[0] and clears the slot.  An fp32 atomic per workgroup on out[0] itself would round
+// the running total once per workgroup: 0.7e-6 .. 2e-6 of the sum at a million elements, different from run to run.  The
+// workgroups spread their sums over the replicas, each on a 128-byte line of its own like the ticket, so that no line takes
+// more atomics than out[0] would.  Launches that may be in flight together must not share a slot: the launcher hands them
+// out in turn.
 #pragma once
 #include "dj_common.h"
 

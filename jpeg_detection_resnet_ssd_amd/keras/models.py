@@ -461,33 +461,13 @@ class Model(object):
         scale = 1.0
         if self.dist is not None:
             scale = self.dist.finish_gradients(plan if plan is not None else self._last_train_plan)
-        if isinstance(opt, optimizers.SGD):
-            lr_t = opt.current_lr()
-
-            def update(a, b, l2, ssq):
-                call("dj_sgd_momentum_update", st["flat"][a:b], st["grads"][a:b], st["vel"][a:b], b - a, lr_t,
-                     opt.momentum, int(opt.nesterov), l2, scale, ssq)
-        elif isinstance(opt, optimizers.Adam):
-            lr_t = opt.step_size()
-            m, v = self._optimizer_buffer("ms"), self._optimizer_buffer("vs")
-            vhat = self._optimizer_buffer("vhats") if opt.amsgrad else None
-
-            def update(a, b, l2, ssq):
-                call("dj_adam_update", st["flat"][a:b], st["grads"][a:b], m[a:b], v[a:b],
-                     vhat[a:b] if vhat is not None else None, b - a, lr_t, opt.beta_1, opt.beta_2, opt.epsilon, l2, scale,
-                     ssq)
-        else:
-            lr_t = opt.current_lr()
-            acc, dacc = self._optimizer_buffer("accumulators"), self._optimizer_buffer("delta_accumulators")
-
-            def update(a, b, l2, ssq):
-                call("dj_adadelta_update", st["flat"][a:b], st["grads"][a:b], acc[a:b], dacc[a:b], b - a, lr_t, opt.rho,
-                     1.0 - opt.rho, opt.epsilon, l2, scale, ssq)
+        entry, state, scalars = opt.update_call(self._optimizer_buffer)
         st["sumsq"].zero_()
         for i, (a, b, l2) in enumerate(st["segments"]):
             if b <= a:
                 continue
-            update(a, b, l2, st["sumsq"][i:i + 1] if l2 else None)
+            call(entry, st["flat"][a:b], st["grads"][a:b], *[s[a:b] if s is not None else None for s in state], b - a,
+                 *scalars, l2, scale, st["sumsq"][i:i + 1] if l2 else None)
         opt.iterations += 1
 
     # ---- optimizer state (Optimizer.get_weights / set_weights) -----------------------------

@@ -4,17 +4,27 @@ SGD (differs from torch.optim.SGD whenever the learning rate changes): lr_t = lr
 v = momentum*v - lr_t*g; p += v  (or p += momentum*v - lr_t*g with nesterov=True).
 Call sites: localisation_part/training_dct_pascal_j2d_resnet.py:152,
 classification_part/config/resnet/config_file.py:58-63.
-
 Adam and Adadelta.  Call sites: localisation_part/evaluation.py:102 and inference.py:104 (Adam(lr=0.001, beta_1=0.9,
-beta_2=0.999, epsilon=1e-08, decay=0.0)); classification_part/template_keras/config/template_config.py (Adadelta).  Keras is
-not a dependency: `adam_host` and `adadelta_host` below are the statement of both rules, in numpy, and csrc/dj_optim.hip
-equals them bit for bit.  All tensor arithmetic is float32; every product, sum, quotient and square root is rounded once,
-in the order written (fl); nothing is fused.  Both share the head of the SGD kernel, the effective gradient
+beta_2=0.999, epsilon=1e-08, decay=0.0)); classification_part/template_keras/config/template_config.py (Adadelta).
+
+Keras is not a dependency: `sgd_host`, `adam_host` and `adadelta_host` below are the statement of the three rules, in numpy,
+and csrc/dj_optim.hip equals them bit for bit.  All tensor arithmetic is float32; every product, sum, quotient and square
+root is rounded once, in the order written (fl); nothing is fused but the two fma of SGD, which round a*b + c once.
+grad_scale is the data-parallel 1/world and l2 the segment's kernel_regularizer (in Keras the penalty is part of the loss,
+so it enters the moments; 0 for un-regularised segments -- a product all the same, so p = Inf gives NaN).
+
+SGD (the roundings are those of the kernel SGD had before it was stated here, which its compiler chose; l2 + l2 is exact):
+
+    t   = fl( fl32(l2 + l2) * p )
+    g'  = fma(g, grad_scale, t)
+    v   = fl( fl(momentum * v) - fl(lr_t * g') )
+    p   = fl( fma(momentum, v, p) - fl(lr_t * g') )  with nesterov,  else  fl(p + v)
+
+with lr_t = lr / (1 + decay * iterations) in Python float64 (SGD.current_lr()), rounded once to float32 by the caller.
+
+Adam and Adadelta share an effective gradient that, unlike SGD's g', rounds both products:
 
     g' = fl( fl(g * grad_scale) + fl( fl32(2*l2) * p ) )
-
-where grad_scale is the data-parallel 1/world and l2 the segment's kernel_regularizer (in Keras the penalty is part of the
-loss, so it enters the moments; 0 for un-regularised segments -- a product all the same, so p = Inf gives NaN).
 
 Adam (Keras holds the betas as float32 variables, so 1 - beta is a float32 subtraction):
 
@@ -65,6 +75,34 @@ def effective_gradient_host(p, g, l2, grad_scale):
         return g * _f32(grad_scale) + (_f32(2.0) * _f32(l2)) * p
 
 
+def fma32(a, b, c):
+    """fl32(a*b + c) of float32 operands, rounded once.  The float64 product of two float32 is exact; TwoSum gives the
+    float64 sum s and its exact error; where the sum is inexact s is moved to its odd neighbour on the side of the error
+    (round to odd), after which the rounding to float32 cannot go wrong.  (fl32 of the float64 a*b + c rounds twice.)"""
+    a, b, c = (np.asarray(t, np.float32).astype(np.float64) for t in (a, b, c))
+    with np.errstate(all="ignore"):
+        x = a * b
+        s = np.asarray(x + c)
+        t = s - x
+        err = (x - (s - t)) + (c - t)
+        even = (s.view(np.int64) & 1) == 0
+        odd_neighbour = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))
+        return np.where(np.isfinite(s) & (err != 0) & even, odd_neighbour, s).astype(np.float32)
+
+
+def sgd_host(p, g, v, lr_t, momentum, nesterov, l2, grad_scale):
+    """One SGD step as the module docstring states it -> (p, v)."""
+    p, g, v = (np.asarray(t, np.float32) for t in (p, g, v))
+    lr_t, momentum = _f32(lr_t), _f32(momentum)
+    with np.errstate(all="ignore"):
+        ge = fma32(g, _f32(grad_scale), (_f32(l2) + _f32(l2)) * p)
+        step = lr_t * ge
+        v = momentum * v - step
+        p = fma32(momentum, v, p) - step if nesterov else p + v
+    assert p.dtype == v.dtype == np.float32
+    return p, v
+
+
 def adam_host(p, g, m, v, vhat, lr_t, beta_1, beta_2, epsilon, l2, grad_scale):
     """One Adam step as the module docstring states it -> (p, m, v, vhat); vhat None = no amsgrad (None is returned)."""
     p, m, v = (np.asarray(t, np.float32) for t in (p, m, v))
@@ -108,6 +146,12 @@ def _check_kwargs(kwargs, strict):
 
 class Optimizer(object):
     state_names = ()        # the per-weight state lists of get_weights(), in Keras' order
+
+    def update_call(self, buffer):
+        """The update kernel's entry point, its state buffers (`buffer(name)` gives the flat buffer of a state list; None
+        for one the entry point takes as NULL) and the scalars of the coming step.  Every entry point is called as
+        (param, grad, *state, n, *scalars, l2, grad_scale, sumsq)."""
+        raise NotImplementedError
 
     def _bind(self, model):
         self._model = weakref.ref(model)
@@ -163,6 +207,9 @@ class SGD(Optimizer):
             lr = lr * (1.0 / (1.0 + self.decay * self.iterations))
         return lr
 
+    def update_call(self, buffer):
+        return "dj_sgd_momentum_update", [buffer("moments")], (self.current_lr(), self.momentum, int(self.nesterov))
+
     def get_config(self):
         return {"lr": self.lr, "momentum": self.momentum, "decay": self.decay, "nesterov": self.nesterov}
 
@@ -192,6 +239,10 @@ class Adam(Optimizer):
         t = self.iterations + 1
         return self.current_lr() * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
+    def update_call(self, buffer):
+        return ("dj_adam_update", [buffer("ms"), buffer("vs"), buffer("vhats") if self.amsgrad else None],
+                (self.step_size(), self.beta_1, self.beta_2, self.epsilon))
+
     def get_config(self):
         return {"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay, "epsilon": self.epsilon,
                 "amsgrad": self.amsgrad}
@@ -214,6 +265,10 @@ class Adadelta(Optimizer):
         if self.initial_decay > 0:
             lr = lr / (1.0 + self.decay * self.iterations)
         return lr
+
+    def update_call(self, buffer):
+        return ("dj_adadelta_update", [buffer("accumulators"), buffer("delta_accumulators")],
+                (self.current_lr(), self.rho, 1.0 - self.rho, self.epsilon))
 
     def get_config(self):
         return {"lr": self.lr, "rho": self.rho, "decay": self.decay, "epsilon": self.epsilon}

@@ -1,6 +1,6 @@
 """Cases shared by tests/test_loss_head_cases_cpu.py and tests/test_loss_head_gpu.py: the code paths of csrc/dj_loss.hip
-(softmax, the SSD multibox loss with batch-wide hard-negative mining, categorical cross-entropy, the Keras SGD update, global
-average pooling), the inputs that reach them and plain float64 references.
+(softmax, the SSD multibox loss with batch-wide hard-negative mining, categorical cross-entropy, global average pooling) and
+of the Keras SGD update (a rule of csrc/dj_optim.hip), the inputs that reach them and plain float64 references.
 
 No GPU is imported here.  Every output operand is a `Slab` (tests/norm_edge_cases.py): a view inside a wider buffer filled
 with one quiet-NaN bit pattern, so that everything around an output can be compared bit for bit after a launch.
@@ -25,15 +25,17 @@ import numpy as np
 import torch
 
 from norm_edge_cases import SENTINEL_BITS, Slab, dyadic, f64, rng_for   # noqa: F401 (re-exported to the two test files)
+from optimizer_cases import several_passes
 from oracle import keras_ops as ko
 
 MARGIN = 8.0
 FLOOR = 2.0 ** -21
 
 # --------------------------------------------------------------------------------------------------------------------
-# launcher rules, copied from csrc/dj_loss.hip
+# launcher rules, copied from csrc/dj_loss.hip (SGD_GROUPS_PER_PASS: from csrc/dj_optim.hip)
 # --------------------------------------------------------------------------------------------------------------------
-EW_BLOCK_CAP = 4096      # ew_blocks: workgroups of 256 threads of the grid-stride kernels (SGD, GAP, the SSD backward)
+EW_BLOCK_CAP = 4096      # ew_blocks: workgroups of 256 threads of the grid-stride kernels (GAP, the SSD backward)
+SGD_GROUPS_PER_PASS = 2048 * 256     # dj_optim_groups_per_pass(): threads of the capped grid, each a group of four elements
 LOSS_BLOCKS = 512        # DJ_LOSS_BLOCKS: the per-box pass
 MINE_BLOCKS = 256        # DJ_MINE_BLOCKS: the histogram and mark kernels
 DJ_HB = 2048             # bins of a histogram level (levels 0 and 1; level 2 uses 1024 of them)
@@ -201,7 +203,7 @@ def gap_bwd_scale(dy, HW, dx0, beta):
 # --------------------------------------------------------------------------------------------------------------------
 # SGD
 # --------------------------------------------------------------------------------------------------------------------
-SGD_N = [1, 63, 257, 4096 * 256 + 5]
+SGD_N = [1, 63, 257, several_passes(SGD_GROUPS_PER_PASS)]
 SGD_SUMSQ0 = 3.5
 # lr_t, momentum values, l2 values, grad_scale values; the dyadic ones are powers of two
 SGD_SCALARS = {"dyadic": (0.25, (0.0, 0.5), (0.0, 0.25), (1.0, 0.125)),
@@ -210,15 +212,20 @@ SgdCfg = collections.namedtuple("SgdCfg", "lr_t momentum nesterov l2 grad_scale 
 
 
 def sgd_configs(n, kind):
-    """Every combination of nesterov, sumsq given / null, momentum, l2 and grad_scale; past the grid (n > 4096*256) six of
-    them, in which every value of every parameter occurs with both values of nesterov."""
+    """Every combination of nesterov, sumsq given / null, momentum, l2 and grad_scale; past the grid (more groups of four
+    than SGD_GROUPS_PER_PASS) six of them, in which every value of every parameter occurs with both values of nesterov."""
     lr_t, moms, l2s, gss = SGD_SCALARS[kind]
-    if n <= EW_BLOCK_CAP * THREADS:
+    if sgd_groups(n) <= SGD_GROUPS_PER_PASS:
         picks = itertools.product((0, 1), (True, False), (0, 1), (0, 1), (0, 1))
     else:   # nesterov, sumsq, index of momentum, of l2, of grad_scale
         picks = [(0, True, 1, 1, 1), (0, False, 0, 0, 0), (0, True, 0, 1, 0), (1, True, 1, 0, 1), (1, False, 0, 1, 0),
                  (1, True, 0, 0, 1)]
     return [SgdCfg(lr_t, moms[a], nes, l2s[b], gss[c], ss) for nes, ss, a, b, c in picks]
+
+
+def sgd_groups(n):
+    """One thread per group of four consecutive elements."""
+    return (n + 3) // 4
 
 
 def sgd_input(n, kind):
@@ -665,7 +672,7 @@ def path_witnesses():
             w["sgd_n1"].append(n)
         if 1 < n < 64:
             w["sgd_n_lt_64"].append(n)
-        if n > EW_BLOCK_CAP * THREADS:
+        if sgd_groups(n) > SGD_GROUPS_PER_PASS:
             w["sgd_grid_stride"].append(n)
         for kind in SGD_SCALARS:
             for c in sgd_configs(n, kind):

@@ -1,5 +1,5 @@
 """Cases shared by tests/test_optimizers_cpu.py and tests/test_optimizers_gpu.py: sizes, scalar sets, inputs and
-special-value rows for the Adam and Adadelta updates, the same rules written once more in float64, and the error bound of
+special-value rows for the SGD, Adam and Adadelta updates, the Adam and Adadelta rules written once more in float64, and the error bound of
 the float32 statement (keras/optimizers.py) against that float64 evaluation.  No GPU is imported here.
 
 The float64 evaluations below do not call the statement: they are the Keras 2.2.4 rules typed again, on the scalars the
@@ -35,16 +35,22 @@ def several_passes(groups_per_pass):
     return 4 * int(groups_per_pass) + 4 * 1000 + 3
 
 
-# lr per step: Adam takes lr_t (Adam.step_size()), Adadelta the decayed lr.  "dyadic": every scalar exact in float32.
+# lr per step: Adam takes lr_t (Adam.step_size()), Adadelta and SGD the decayed lr.  "dyadic": every scalar exact in float32.
 SCALAR_SETS = {
     "dyadic": dict(adam=dict(lr_t=[2.0 ** -6] * STEPS, beta_1=0.5, beta_2=0.5, epsilon=2.0 ** -8),
                    adadelta=dict(lr=[0.5] * STEPS, rho=0.5, epsilon=2.0 ** -10),
+                   sgd=dict(lr_t=[0.25] * STEPS, momentum=(0.0, 0.5)),
                    l2=(0.0, 2.0 ** -4), grad_scale=(1.0, 0.125)),
     "normal": dict(adam=dict(lr_t=[0.001 / (1 + 1e-4 * i) * math.sqrt(1 - 0.999 ** (i + 1)) / (1 - 0.9 ** (i + 1))
                                    for i in range(STEPS)], beta_1=0.9, beta_2=0.999, epsilon=1e-7),
                    adadelta=dict(lr=[1.0 / (1 + 1e-4 * i) for i in range(STEPS)], rho=0.95, epsilon=1e-7),
+                   sgd=dict(lr_t=[0.1 / (1 + 1e-4 * i) for i in range(STEPS)], momentum=(0.0, 0.9)),
                    l2=(0.0, 5e-4), grad_scale=(1.0, 0.125)),
 }
+
+# SGD beyond the small sizes: (nesterov, index of momentum, of l2, of grad_scale); every value of every parameter occurs with
+# both values of nesterov
+SGD_FEW = [(0, 1, 1, 1), (0, 0, 0, 0), (0, 0, 1, 0), (1, 1, 0, 1), (1, 0, 1, 0), (1, 0, 0, 1)]
 
 
 def inputs(n, kind, seed=5):

@@ -78,7 +78,10 @@ def test_gap_cases():
 
 
 def test_sgd_cases():
-    assert lc.SGD_N == [1, 63, 257, 4096 * 256 + 5] and lc.ew_blocks(lc.SGD_N[-1]) == 4096
+    assert lc.SGD_GROUPS_PER_PASS == 2048 * 256 and lc.SGD_N == [1, 63, 257, 4 * 2048 * 256 + 4003]
+    assert [lc.sgd_groups(n) for n in (1, 4, 5)] == [1, 1, 2]
+    assert lc.sgd_groups(lc.SGD_N[-1]) > lc.SGD_GROUPS_PER_PASS >= lc.sgd_groups(lc.SGD_N[-2])      # threads take a second group
+    assert lc.SGD_N[-1] % 4 == 3                                                                    # and the last group is partial
     for kind in lc.SGD_SCALARS:
         full = lc.sgd_configs(257, kind)
         assert len(set(full)) == 32

@@ -1,4 +1,4 @@
-"""Every code path of csrc/dj_loss.hip against the float64 references of tests/loss_head_cases.py: the dead tail and every
+"""Every code path of csrc/dj_loss.hip, and the SGD rule of csrc/dj_optim.hip, against the float64 references of tests/loss_head_cases.py: the dead tail and every
 group size of the softmax kernels, the per-box pass, the mining selection at every k of a case built around its three radix
 levels and its tie tickets, the backward of the SSD loss, categorical cross-entropy at its clips, the SGD update and global
 average pooling past their grids.
@@ -309,9 +309,12 @@ def test_categorical_crossentropy(rows, C, cuda, E):
 @pytest.mark.parametrize("kind", list(lc.SGD_SCALARS))
 @pytest.mark.parametrize("n", lc.SGD_N)
 def test_sgd(n, kind, cuda, E):
-    """p, v and the sum of squares.  Past the grid (n = 4096*256 + 5) 4096 workgroups contribute to the sum: one fp32 atomic
-    each on sumsq[0] left 0.7e-6 .. 2.1e-6 of the sum there, different from run to run, against a bound of 4.77e-7 (normal
-    data) and 1.35e-6 (dyadic data); the kernel now adds the workgroups' sums in fp64 and rounds once."""
+    """p, v and the sum of squares.  The three buffers sit at element offsets 1, 2 and 3 of their allocations, so every
+    launch here takes the element-by-element path (tests/test_optimizers_gpu.py has the 16-byte one).  Past the grid (more
+    groups of four than one pass of the capped grid covers) 2048 workgroups contribute to the sum: one fp32 atomic each on
+    sumsq[0] would round the running total once per workgroup, different from run to run; the kernel adds the workgroups'
+    sums in fp64 and rounds once."""
+    assert lc.SGD_GROUPS_PER_PASS == E._lib.load().dj_optim_groups_per_pass()
     p0, g0, v0 = lc.sgd_input(n, kind)
     g = dense(g0, cuda, 3)
     for cfg in lc.sgd_configs(n, kind):

@@ -1,13 +1,15 @@
 """keras.optimizers.Adam / Adadelta without a GPU: compile() accepts them, the classes' surface, and the float32 statement
 (adam_host, adadelta_host) pinned independently of itself -- against the rules typed again in float64
 (tests/optimizer_cases.py), exactly where every operation is exact and within the derived bound elsewhere, and against
-known answers worked out by hand."""
+known answers worked out by hand.  SGD's statement (sgd_host): its fma against an evaluation in integers, the step against
+the oracle's (tests/loss_head_cases.py), exactly on dyadic data and within that file's bound elsewhere."""
 import math
 import os
 
 import numpy as np
 import pytest
 
+import loss_head_cases as lc
 import optimizer_cases as oc
 
 
@@ -234,6 +236,136 @@ def test_nan_and_inf_propagate():
     assert adadelta_host([1.5], [0.0], [0.0], [0.0], 1.0, 0.95, 1e-7, 0.0, 1.0)[0][0] == np.float32(1.5)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# SGD
+# ----------------------------------------------------------------------------------------------------------------------
+def _int_parts(x):
+    """A finite float32 as m * 2^e with m an integer."""
+    m, e = math.frexp(float(x))
+    return int(m * 2 ** 24), e - 24
+
+
+def _round_to_f32(n, e):
+    """n * 2^e (n any Python integer) rounded to the nearest float32, ties to even, with denormals and overflow."""
+    if n == 0:
+        return np.float32(0.0)
+    sign, n = (-1.0 if n < 0 else 1.0), abs(n)
+    q = max(n.bit_length() - 1 + e - 23, -149)          # exponent of the last place kept
+    shift = q - e
+    if shift <= 0:
+        r, q = n, e
+    else:
+        r, rem, half = n >> shift, n & ((1 << shift) - 1), 1 << (shift - 1)
+        if rem > half or (rem == half and r & 1):
+            r += 1
+    if r.bit_length() + q > 128:
+        return np.float32(sign * np.inf)
+    return np.float32(sign * math.ldexp(r, q))
+
+
+def _exact_fma(a, b, c):
+    (ma, ea), (mb, eb), (mc, ec) = _int_parts(a), _int_parts(b), _int_parts(c)
+    e = min(ea + eb, ec)
+    return _round_to_f32((ma * mb << (ea + eb - e)) + (mc << (ec - e)), e)
+
+
+def _fma_traps():
+    """a*b + c whose exact value lies within 2^-60 (relative) of the midpoint of two float32 values, on either side of it:
+    a*b = 2^16 (1 - k^2 2^-46) and c = +-C 2^17, C an integer of 24 bits.  The float64 sum of the exact product and c is the
+    midpoint itself, so rounding it to float32 goes to the even neighbour whatever the side."""
+    out = []
+    for k in (1, 2, 3, 7, 32):
+        a, b = np.float32(256 * (1 + k * 2.0 ** -23)), np.float32(256 * (1 - k * 2.0 ** -23))
+        for C in (2 ** 23 + 1, 2 ** 23 + 2, 2 ** 23 + 5, 2 ** 24 - 1, 2 ** 24 - 2, 12345678, 12345679):
+            for sa in (1, -1):
+                for sc in (1, -1):
+                    out.append((np.float32(sa) * a, b, np.float32(sc * C * 2.0 ** 17)))
+    return out
+
+
+def test_fma32_equals_the_evaluation_in_integers_on_random_triples():
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import fma32
+    rng = np.random.default_rng(11)
+    n = 4000
+    mant = lambda: (rng.integers(2 ** 23, 2 ** 24, n) * rng.choice([-1.0, 1.0], n))
+    a = (mant() * 2.0 ** rng.integers(-40, 10, n)).astype(np.float32)
+    b = (mant() * 2.0 ** rng.integers(-40, 10, n)).astype(np.float32)
+    c = (mant() * 2.0 ** rng.integers(-60, 10, n)).astype(np.float32)
+    near = rng.random(n) < 0.5          # half of them cancel: c within a few float32 ulp of -a*b
+    c[near] = (-(a[near].astype(np.float64) * b[near]) * (1 + rng.integers(-4, 5, near.sum()) * 2.0 ** -23)).astype(np.float32)
+    tiny = rng.random(n) < 0.1          # results among the float32 denormals
+    a[tiny] = (a[tiny].astype(np.float64) * 2.0 ** -100).astype(np.float32)
+    c[tiny] = (c[tiny].astype(np.float64) * 2.0 ** -100).astype(np.float32)
+    huge = np.arange(n) % 97 == 0       # overflow
+    a[huge], b[huge] = np.float32(2.0 ** 100), np.float32(3.0 * 2.0 ** 27)
+    got = fma32(a, b, c)
+    want = np.array([_exact_fma(*t) for t in zip(a, b, c)], np.float32)
+    assert got.dtype == np.float32 and np.array_equal(got, want)
+    assert np.isinf(want).any() and ((want != 0) & (np.abs(want) < np.finfo(np.float32).tiny)).any()
+    assert ((want != 0) & (np.abs(want) < 2.0 ** -20 * np.abs(c))).any()             # cancellation did happen
+    # by hand: 1 + 2^-24 is a tie (to even: 1), anything above it is not
+    one, h = np.float32(1), np.float32(2.0 ** -12)
+    assert fma32(h, h, one) == one and fma32(h, np.float32(2.0 ** -12 + 2.0 ** -35), one) == np.float32(1 + 2.0 ** -23)
+    assert np.isnan(fma32(np.float32(np.inf), np.float32(0), one)) and fma32(np.float32(np.inf), one, one) == np.inf
+
+
+def test_fma32_at_double_rounding_traps():
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import fma32
+    traps = _fma_traps()
+    wrong = 0
+    for a, b, c in traps:
+        (ma, ea), (mb, eb), (mc, ec) = _int_parts(a), _int_parts(b), _int_parts(c)
+        e = min(ea + eb, ec)
+        exact = (ma * mb << (ea + eb - e)) + (mc << (ec - e))           # the value is exact * 2^e
+        want = _exact_fma(a, b, c)
+        mw, ew = _int_parts(want)
+        near = mw << (ew - e)                                           # the float32 it rounds to, and the one on the other side
+        other = np.nextafter(want, np.float32(np.inf if exact > near else -np.inf))
+        mo, eo = _int_parts(other)
+        twice_mid = near + (mo << (eo - e))
+        dist = abs(2 * exact - twice_mid)                               # twice the distance to the midpoint
+        assert 0 < dist and dist << 60 <= 2 * abs(exact), (a, b, c)
+        assert fma32(a, b, c) == want and fma32(b, a, c) == want, (a, b, c)
+        wrong += int(np.float32(np.float64(a) * np.float64(b) + np.float64(c)) != want)
+    assert len(traps) >= 100 and wrong >= len(traps) // 4        # the float64 expression rounded to float32 falls into them
+
+
+def test_sgd_statement_equals_the_oracle_on_dyadic_data():
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import sgd_host
+    for n in (63, 257):
+        p, g, v = lc.sgd_input(n, "dyadic")
+        for cfg in lc.sgd_configs(n, "dyadic"):
+            p64, v64 = lc.ref_sgd(p, g, v, cfg)
+            pn, vn = sgd_host(p, g, v, cfg.lr_t, cfg.momentum, cfg.nesterov, cfg.l2, cfg.grad_scale)
+            assert pn.dtype == vn.dtype == np.float32
+            assert np.array_equal(pn.astype(np.float64), p64) and np.array_equal(vn.astype(np.float64), v64), cfg
+    assert not np.array_equal(pn, p)
+
+
+def test_sgd_statement_stays_within_the_bound_of_the_loss_head_cases():
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import sgd_host
+    import torch
+    for n in (63, 257):
+        p, g, v = lc.sgd_input(n, "normal")
+        for cfg in lc.sgd_configs(n, "normal"):
+            p64, v64 = lc.ref_sgd(p, g, v, cfg)
+            p32, v32 = lc.ref_sgd(p, g, v, cfg, torch.float32)
+            sp, sv = lc.sgd_scales(p, g, v, cfg)
+            pn, vn = sgd_host(p, g, v, cfg.lr_t, cfg.momentum, cfg.nesterov, cfg.l2, cfg.grad_scale)
+            assert lc.rel_err(pn, p64, sp) <= lc.bound(p32, p64, sp), cfg
+            assert lc.rel_err(vn, v64, sv) <= lc.bound(v32, v64, sv), cfg
+
+
+def test_sgd_known_answers():
+    """Nothing rounds: g' = 8 * 0.25 + 2 * 0.5 * 2 = 4; v = 0.5 * 2 - 0.25 * 4 = 0; with v0 = 6: v = 2, p = 2 + 2, and with
+    nesterov p = 2 + 0.5 * 2 - 1 = 2."""
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import sgd_host
+    assert [float(t[0]) for t in sgd_host([2.0], [8.0], [2.0], 0.25, 0.5, False, 0.5, 0.25)] == [2.0, 0.0]
+    assert [float(t[0]) for t in sgd_host([2.0], [8.0], [6.0], 0.25, 0.5, False, 0.5, 0.25)] == [4.0, 2.0]
+    assert [float(t[0]) for t in sgd_host([2.0], [8.0], [6.0], 0.25, 0.5, True, 0.5, 0.25)] == [2.0, 2.0]
+    assert np.isnan(sgd_host([np.inf], [0.25], [0.0], 0.1, 0.9, False, 0.0, 1.0)[0][0])       # 0 * Inf in the penalty
+
+
 def test_get_weights_needs_a_compiled_model():
     from jpeg_detection_resnet_ssd_amd.keras.optimizers import Adam
     with pytest.raises(RuntimeError, match="compile"):
@@ -252,7 +384,7 @@ def _built_lib():
 def test_library_exports_the_entry_points_and_keeps_its_abi_version():
     from jpeg_detection_resnet_ssd_amd import _lib
     lib = _built_lib()
-    for name in ("dj_adam_update", "dj_adadelta_update", "dj_optim_groups_per_pass"):
+    for name in ("dj_sgd_momentum_update", "dj_adam_update", "dj_adadelta_update", "dj_optim_groups_per_pass"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert lib.dj_abi_version() == 4 and _lib.ABI_VERSION == 4
     assert lib.dj_optim_groups_per_pass() > 0 and lib.dj_optim_groups_per_pass() % 256 == 0
@@ -275,3 +407,9 @@ def test_argument_checks_refuse_before_any_launch():
     for (p, g, a, d, n) in bad_adadelta:
         assert lib.dj_adadelta_update(p, g, a, d, n, *sd, None, None) == -1, (p, g, a, d, n)
         assert b"dj_adadelta_update" in lib.dj_last_error()
+    ss = (0.1, 0.9, 1, 5e-4, 1.0)
+    bad_sgd = [(None, G, V, 64), (P, None, V, 64), (P, G, None, 64), (P, G, V, 0), (P, G, V, -4), (P, G, P, 64), (P, P, V, 64),
+               (P, G, P + 4 * 63, 64), (P, G, G, 64)]
+    for (p, g, v, n) in bad_sgd:
+        assert lib.dj_sgd_momentum_update(p, g, v, n, *ss, S, None) == -1, (p, g, v, n)
+        assert b"dj_sgd_momentum_update" in lib.dj_last_error()

@@ -1,4 +1,4 @@
-"""dj_adam_update / dj_adadelta_update against the host statement (keras/optimizers.py), bit for bit, and the optimizers
+"""dj_sgd_momentum_update / dj_adam_update / dj_adadelta_update against the host statement (keras/optimizers.py), bit for bit, and the optimizers
 behind Model.compile: sizes around the group of four and the tail, a size that takes the grid-stride loop round more than
 once, a base pointer that is not 16-byte aligned, both scalar sets with and without l2 and grad_scale, amsgrad, three
 chained steps, special values, the sum of squares, the argument checks, teacher-forced training steps of a small model
@@ -71,6 +71,29 @@ def _adadelta_launch(b, n, lr, k, l2, scale, sumsq=None):
     call("dj_adadelta_update", b["p"], b["g"], b["a"], b["d"], n, lr, k["rho"], 1.0 - k["rho"], k["epsilon"], l2, scale, sumsq)
 
 
+def _sgd_launch(b, n, lr_t, momentum, nesterov, l2, scale, sumsq=None):
+    from jpeg_detection_resnet_ssd_amd.engine import call
+    call("dj_sgd_momentum_update", b["p"], b["g"], b["v"], n, lr_t, momentum, int(nesterov), l2, scale, sumsq)
+
+
+def _sgd_chain(cuda, n, kind, off, l2, scale, momentum, nesterov, p0, gs, steps=oc.STEPS):
+    """The velocity starts from the last gradient, so that the first step already multiplies something."""
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import sgd_host
+    lr = oc.SCALAR_SETS[kind]["sgd"]["lr_t"]
+    b = Buffers(cuda, off, p=p0, g=gs[0], v=gs[-1])
+    p, v = p0, gs[-1]
+    for t in range(steps):
+        if t:
+            b["g"][:n].copy_(torch.from_numpy(gs[t]))
+        _sgd_launch(b, n, lr[t], momentum, nesterov, l2, scale)
+        p, v = sgd_host(p, gs[t], v, lr[t], momentum, nesterov, l2, scale)
+        what = "sgd n=%d %s off=%d l2=%g scale=%g momentum=%g nesterov=%d step %d: " % (n, kind, off, l2, scale, momentum,
+                                                                                      nesterov, t)
+        _same_bits(b.host("p", n), p, what + "p")
+        _same_bits(b.host("v", n), v, what + "v")
+        _same_bits(b.host("g", n), gs[t], what + "g")
+
+
 def _adam_chain(cuda, n, kind, off, l2, scale, amsgrad, p0, gs):
     from jpeg_detection_resnet_ssd_amd.keras.optimizers import adam_host
     k = oc.SCALAR_SETS[kind]["adam"]
@@ -119,6 +142,9 @@ def test_kernels_equal_the_host_statement(cuda, n):
                     for amsgrad in (False, True):
                         _adam_chain(cuda, n, kind, off, l2, scale, amsgrad, p0, gs)
                     _adadelta_chain(cuda, n, kind, off, l2, scale, p0, gs)
+                    for momentum in sc["sgd"]["momentum"]:
+                        for nesterov in (False, True):
+                            _sgd_chain(cuda, n, kind, off, l2, scale, momentum, nesterov, p0, gs)
 
 
 def test_several_passes_of_the_capped_grid(cuda):
@@ -129,11 +155,27 @@ def test_several_passes_of_the_capped_grid(cuda):
     _adadelta_chain(cuda, n, "normal", 0, 5e-4, 0.125, p0, gs)
 
 
+def test_several_passes_of_the_capped_grid_sgd(cuda):
+    """One step of each of the six configurations of optimizer_cases.SGD_FEW, on the 16-byte path."""
+    n = oc.several_passes(_gpp())
+    sc = oc.SCALAR_SETS["normal"]
+    p0, gs = oc.inputs(n, "normal")
+    for nesterov, a, b, c in oc.SGD_FEW:
+        _sgd_chain(cuda, n, "normal", 0, sc["l2"][b], sc["grad_scale"][c], sc["sgd"]["momentum"][a], nesterov, p0, gs, steps=1)
+
+
 def test_a_single_misaligned_pointer_takes_the_fallback(cuda):
     """Only the state buffers are offset: the launcher must look at every pointer."""
-    from jpeg_detection_resnet_ssd_amd.keras.optimizers import adadelta_host, adam_host
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import adadelta_host, adam_host, sgd_host
     n = 1021
     p0, gs = oc.inputs(n, "normal")
+    for odd in ("v", "p", "g"):
+        for nesterov in (False, True):
+            b = Buffers(cuda, 0, p=p0, g=gs[0], v=gs[1])
+            b.t[odd] = Buffers(cuda, 1, x=dict(p=p0, g=gs[0], v=gs[1])[odd])["x"]
+            _sgd_launch(b, n, 0.1, 0.9, nesterov, 5e-4, 1.0)
+            for name, w in zip(("p", "v"), sgd_host(p0, gs[0], gs[1], 0.1, 0.9, nesterov, 5e-4, 1.0)):
+                _same_bits(b.host(name, n), w, "sgd, %s offset: %s" % (odd, name))
     k = oc.SCALAR_SETS["normal"]["adam"]
     z = np.zeros(n, np.float32)
     for odd in ("p", "g", "m", "v", "vhat"):
@@ -156,10 +198,18 @@ def test_a_single_misaligned_pointer_takes_the_fallback(cuda):
 def test_special_values(cuda):
     """g = 0 on zero state, +-Inf, NaN, p = Inf with l2 = 0, gradients whose square is a float32 denormal, signed zeros and
     a large second moment: whatever the statement gives (checked by hand in tests/test_optimizers_cpu.py), bit for bit."""
-    from jpeg_detection_resnet_ssd_amd.keras.optimizers import adadelta_host, adam_host
+    from jpeg_detection_resnet_ssd_amd.keras.optimizers import adadelta_host, adam_host, sgd_host
     p0, g, second = oc.special_inputs()
     n = len(p0)
     z = np.zeros(n, np.float32)
+    for off in (0, 1):
+        for nesterov in (False, True):
+            b = Buffers(cuda, off, p=p0, g=g, v=second)
+            _sgd_launch(b, n, 0.1, 0.9, nesterov, 0.0, 1.0)
+            want = sgd_host(p0, g, second, 0.1, 0.9, nesterov, 0.0, 1.0)
+            assert want[0][0] == p0[0] and np.isinf(want[0][1:3]).all() and np.isnan(want[0][3:5]).all()
+            for name, w in zip(("p", "v"), want):
+                _same_bits(b.host(name, n), w, "sgd special values off=%d nesterov=%d: %s" % (off, nesterov, name))
     k = oc.SCALAR_SETS["normal"]["adam"]
     assert 0 < np.float32(1e-20) * np.float32(1e-20) < np.finfo(np.float32).tiny
     for off in (0, 1):
@@ -210,6 +260,22 @@ def test_sum_of_squares(cuda, n):
                 got.append([b.host(name, n) for name in ("p", "m", "v") + (("vhat",) if amsgrad else ())])
             for x, y in zip(*got):
                 _same_bits(x, y, "with and without sumsq")
+        for which in ("sgd", "sgd nesterov"):
+            got = []
+            for with_sum in (True, False):
+                b = Buffers(cuda, off, p=p0, g=gs[0], v=gs[1])
+                ss = torch.full((3,), start, device=cuda)
+                _sgd_launch(b, n, 0.1, 0.9, which != "sgd", 5e-4, 1.0, ss[1:2] if with_sum else None)
+                ssh = ss.cpu().numpy()
+                assert ssh[0] == start and ssh[2] == start
+                if with_sum:
+                    print("%s n=%d off=%d: sumsq relative error %.3g, bound %.3g" % (which, n, off, abs(float(ssh[1]) - exact) / exact, bound))
+                    assert abs(float(ssh[1]) - exact) <= bound * exact
+                else:
+                    assert ssh[1] == start
+                got.append([b.host(name, n) for name in ("p", "v")])
+            for x, y in zip(*got):
+                _same_bits(x, y, "with and without sumsq")
         got = []
         for with_sum in (True, False):
             b = Buffers(cuda, off, p=p0, g=gs[0], a=z, d=z)
@@ -226,7 +292,8 @@ def test_sum_of_squares(cuda, n):
 
 
 def test_sum_of_squares_slots_are_clean_after_many_launches(cuda):
-    """More launches than the library has accumulator slots: each leaves its slot cleared for the next user."""
+    """More launches than the library has accumulator slots, SGD's among Adam's (the slots are shared): each leaves its
+    slot cleared for the next user."""
     n = 1021
     p0, gs = oc.inputs(n, "normal", seed=8)
     z = np.zeros(n, np.float32)
@@ -234,7 +301,10 @@ def test_sum_of_squares_slots_are_clean_after_many_launches(cuda):
     b = Buffers(cuda, 0, p=p0, g=gs[0], m=z, v=z, vhat=None)
     ss = torch.zeros(80, device=cuda)
     for i in range(80):
-        _adam_launch(b, n, 0.0, ka, 0.0, 0.0, ss[i:i + 1])          # lr_t = 0, grad_scale = 0: p stays what it is
+        if i % 3 == 1:
+            _sgd_launch(b, n, 0.0, 0.9, False, 0.0, 0.0, ss[i:i + 1])    # on v = 0: the velocity stays 0 and p what it is
+        else:
+            _adam_launch(b, n, 0.0, ka, 0.0, 0.0, ss[i:i + 1])          # lr_t = 0, grad_scale = 0: p stays what it is
     ssh = ss.cpu().numpy()
     _same_bits(b.host("p", n), p0)
     assert np.all(ssh == ssh[0])
@@ -261,6 +331,12 @@ def test_argument_checks_launch_nothing(cuda):
     for args in bad_adadelta:
         assert lib.dj_adadelta_update(*args, *sd, S, stream) == -1, args
         assert len(lib.dj_last_error()) > 10
+    ssgd = (0.1, 0.9, 1, 5e-4, 1.0)
+    bad_sgd = [(None, G, V, n), (P, None, V, n), (P, G, None, n), (P, G, V, 0),
+               (P, G, P, n), (P, P, V, n), (P, G, P + 4 * (n - 1), n), (P, P - 4 * (n - 1), V, n), (P, G, G, n)]
+    for args in bad_sgd:
+        assert lib.dj_sgd_momentum_update(*args, *ssgd, S, stream) == -1, args
+        assert b"dj_sgd_momentum_update" in lib.dj_last_error()
     torch.cuda.synchronize()
     for name, want in (("p", p0), ("g", gs[0]), ("m", z), ("v", z), ("vhat", z), ("ss", np.zeros(1, np.float32))):
         _same_bits(b.host(name, len(want)), want, name + " after refused calls")

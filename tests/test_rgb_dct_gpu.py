@@ -166,8 +166,9 @@ def test_model_fed_with_pixels_equals_model_fed_with_the_decoded_file(cuda, gold
     The bound is applied to the data loss, the mining counts included: the part of the reported loss that the inputs
     reach.  Measured on an MI355X: data loss 67.548095703125 (deconv) / 32.575592041015625 (ssd_custom) in all three
     runs, spread 0, difference 0.  The other part, the l2 report, is sum(w^2) of the weights BEFORE the step -- the same
-    weights in all three runs, whatever is fed -- accumulated by dj_sgd_momentum_update with fp32 atomics, so its last
-    digit moves from run to run on its own (4.72073779 / 4.72073877 between the two host-fed deconv runs; 3.69233496
+    weights in all three runs, whatever is fed -- accumulated by dj_sgd_momentum_update: per segment the workgroups' sums
+    are added with fp64 atomics, whose order is free, and rounded once to fp32, and float(l2 * sum) is added over the
+    segments, so its last digit may move from run to run on its own (with the fp32 atomics of an earlier kernel: 4.72073779 / 4.72073877 between the two host-fed deconv runs; 3.69233496
     twice, then 3.69233594, for ssd_custom): on the sum, "no more than two host-fed runs differ" is a comparison of
     three draws of that noise and fails about every other time with identical inputs.  The sums are printed."""
     from jpeg_detection_resnet_ssd_amd import workloads

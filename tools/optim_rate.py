@@ -6,7 +6,8 @@ vgga_dct (as laid out in the flat buffer).  Per launch: bytes moved (every strea
     python tools/optim_rate.py                    # the table
     python tools/optim_rate.py --train-step       # also: one SSD300 training step (deconv, B=32) with SGD and with Adam
 
-The yardstick of the new kernels is dj_sgd_momentum_update in the same run: they must not move fewer bytes per second."""
+The three are rules of one kernel (csrc/dj_optim.hip), so none is a yardstick for the others: a change of that kernel is
+measured against the build before it, the two libraries alternating in one session (DJ_LIB_PATH selects the library)."""
 import argparse
 import os
 import sys

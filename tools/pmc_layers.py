@@ -9,7 +9,7 @@ sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.abspath(_
 def last_step_igemm(path, counter):
     rows = [r for r in csv.DictReader(open(path)) if r["Counter_Name"] == counter]
     rows.sort(key=lambda r: int(r["Dispatch_Id"]))
-    sgd = [i for i, r in enumerate(rows) if "dj_sgd" in r["Kernel_Name"]]
+    sgd = [i for i, r in enumerate(rows) if "dj_optim_kernel" in r["Kernel_Name"] or "dj_sgd" in r["Kernel_Name"]]
     loss = [i for i, r in enumerate(rows) if "dj_ssd_loss_bwd" in r["Kernel_Name"]]
     hi = sgd[-1]
     lo = max([i for i in sgd if i < loss[-1]] or [-1]) + 1

@@ -10,7 +10,7 @@ def last_step(path, counter):
     marks = [i for i, r in enumerate(rows) if "dj_ssd_loss_bwd" in r["Kernel_Name"]]
     fwd0 = [i for i, r in enumerate(rows) if "dj_softmax_fwd" in r["Kernel_Name"]]
     # one step = from the sgd of the previous step to the sgd of this one
-    sgd = [i for i, r in enumerate(rows) if "dj_sgd" in r["Kernel_Name"]]
+    sgd = [i for i, r in enumerate(rows) if "dj_optim_kernel" in r["Kernel_Name"] or "dj_sgd" in r["Kernel_Name"]]
     hi = sgd[-1]
     lo = max(i for i in sgd if i < marks[-1] and i < fwd0[-1]) + 1 if any(i < fwd0[-1] for i in sgd) else 0
     return rows[lo:hi + 1]

@@ -745,6 +745,35 @@ int dj_dropout_fwd(const float* x, float* y, long n, unsigned threshold, float s
 int dj_dropout_bwd(const float* dy, float* dx, long n, unsigned threshold, float scale, unsigned key0, unsigned key1,
                    unsigned ctr2, unsigned ctr3, int beta, void* stream);
 
+/* ---- Keras' ImageDataGenerator on a [batch][height][width][3] uint8 tensor -> float32 NHWC: the affine warp, the flips and
+ * the standardisation that `ImageDataGenerator(...).flow_from_directory(...)` of the RGB ResNet50 applies to every loaded
+ * image (C/config/resnetRGB/config_file.py:157-172; per image Keras runs scipy.ndimage.affine_transform(order=1,
+ * mode='nearest') once per channel, in float64).  data/rgb_warp.py:affine_warp_host states the warp and rgb_warp_host the
+ * whole call; the result equals them bit for bit.  Per image one record: m = the top two rows of the recentred matrix M,
+ * row-major; identity != 0: no warp, the pixel's own value; flip_cols / flip_rows: mirror the warped image.  For the pixel
+ * (i, j) of the warped image, everything in float64 with every product and sum rounded on its own:
+ *   r = (m[0]*i + m[1]*j) + m[2], c = (m[3]*i + m[4]*j) + m[5], both clipped to the image; r0 = floor(r), tr = r - r0,
+ *   r1 = min(r0 + 1, height - 1) (columns alike); value = (((x[r0,c0]*(1-tr))*(1-tc) + (x[r0,c1]*(1-tr))*tc)
+ *   + (x[r1,c0]*tr)*(1-tc)) + (x[r1,c1]*tr)*tc, rounded once to float32.
+ * Output pixel (i, j) is the warped pixel (flip_rows ? height-1-i : i, flip_cols ? width-1-j : j).  Then, in float32:
+ * preprocess == DJ_RGB_PREP_CAFFE reverses the channels and subtracts (103.939f, 116.779f, 123.68f); has_rescale != 0
+ * multiplies by `rescale`.  pixels (dense packed RGB) / rec_dev / out are DEVICE pointers, rec_host the HOST copy of the
+ * records, read during the call only.  out: `out_row_stride` floats between pixel rows, images height * out_row_stride
+ * apart, only the 3 * width floats of each row are written.  One thread per four consecutive pixels: three 16-byte stores
+ * where `out` is 16-byte aligned and, with strided rows, out_row_stride is a multiple of 4; element by element otherwise and
+ * in the tail of a run.  Refused before any launch: a NULL pointer, batch / height / width < 1 or a side above 32768,
+ * out_row_stride < 3 * width, an unknown preprocess code, a matrix entry of a non-identity record that is not finite.
+ * One launch, no synchronisation: the call stays capturable. ---- */
+#define DJ_RGB_PREP_NONE 0
+#define DJ_RGB_PREP_CAFFE 1
+typedef struct dj_rgb_warp_record {
+  double m[6];
+  int identity, flip_cols, flip_rows, reserved;
+} dj_rgb_warp_record;
+int dj_rgb_warp(const unsigned char* pixels, int batch, int height, int width, const dj_rgb_warp_record* rec_dev,
+                const dj_rgb_warp_record* rec_host, int preprocess, int has_rescale, float rescale, float* out,
+                long out_row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

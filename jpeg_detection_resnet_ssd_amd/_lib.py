@@ -52,6 +52,10 @@ class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
 
+class RgbWarpRecord(Structure):   # dj_rgb_warp_record
+    _fields_ = [("m", c_double * 6), ("identity", c_int), ("flip_cols", c_int), ("flip_rows", c_int), ("reserved", c_int)]
+
+
 class SsdPhotoParams(Structure):   # dj_ssd_photo_params
     _fields_ = [("sequence", c_int), ("flags", c_int), ("brightness", c_float), ("contrast", c_float), ("saturation", c_float),
                 ("hue", c_float), ("order", c_int * 3), ("reserved", c_int)]
@@ -195,6 +199,8 @@ SIGNATURES = {
     "dj_image_prep": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_long,
                               c_void_p, c_long, c_void_p]),
     "dj_photometric": (c_int, [c_void_p, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dj_rgb_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_long,
+                            c_void_p]),
     "dj_patch_resize_scratch_bytes": (c_long, [c_void_p, c_int, c_int]),
     "dj_patch_resize": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
                                 c_long, c_void_p, c_long, c_void_p]),

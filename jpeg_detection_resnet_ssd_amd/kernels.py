@@ -439,6 +439,34 @@ def photometric(pixels, ops_dev, ops_host, shift_out=None, stream=None):
     return pixels
 
 
+# ---- Keras' ImageDataGenerator on a uint8 batch: affine warp, flips, standardisation -> float32 NHWC -------------------------
+def rgb_warp(pixels, rec_dev, rec_host, out, preprocess=0, rescale=None, stream=None):
+    """dj_rgb_warp: `pixels` a contiguous (B, H, W, 3) uint8 CUDA tensor; `rec_dev` the per-image records' bytes on the
+    device (1-D uint8) and `rec_host` the same records as a numpy array of data/rgb_warp.py:RECORD_DTYPE; `out` a
+    (B, H, W, 3) float32 CUDA tensor whose rows may be strided (images dense); `preprocess` 0 (none) or 1 (caffe: BGR and
+    mean); `rescale` None or the float32 factor.  `stream`: a HIP stream handle (None: the current launch stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import RgbWarpRecord
+    from .data.rgb_warp import RECORD_DTYPE
+    assert RECORD_DTYPE.itemsize == ctypes.sizeof(RgbWarpRecord), "record layouts disagree"
+    assert pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] == 3 \
+        and pixels.is_contiguous(), "pixels: expected a contiguous (B, H, W, 3) uint8 CUDA tensor"
+    b, h, w, _ = pixels.shape
+    assert isinstance(rec_host, np.ndarray) and rec_host.dtype == RECORD_DTYPE and rec_host.shape == (b,) \
+        and rec_host.flags.c_contiguous, "rec_host: expected a contiguous array of one RECORD_DTYPE entry per image"
+    assert rec_dev.is_cuda and rec_dev.dtype == torch.uint8 and rec_dev.dim() == 1 and rec_dev.is_contiguous() \
+        and rec_dev.numel() >= rec_host.nbytes and rec_dev.data_ptr() % 8 == 0, \
+        "rec_dev: expected a contiguous, 8-byte aligned 1-D uint8 CUDA tensor of the records' size"
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (b, h, w, 3), \
+        "out: expected float32 %s, got %s %s" % ((b, h, w, 3), out.dtype, tuple(out.shape))
+    stride = _packed_rgb_stride(out, "out: ")
+    check(_L().dj_rgb_warp(ptr(pixels), b, h, w, ptr(rec_dev), rec_host.ctypes.data, int(preprocess),
+                           int(rescale is not None), float(rescale) if rescale is not None else 1.0, ptr(out), stride,
+                           stream if stream is not None else _stream()), "dj_rgb_warp")
+    return out
+
+
 # ---- ragged batch of decoded images -> a window of each on a background, mirrored, resized -----------------------------------
 def patch_resize(src, desc_dev, desc_host, pool_dev, pool_host, out, scratch, stream=None):
     """dj_patch_resize: `src` 1-D uint8 CUDA tensor holding the staged rectangles, `desc_dev` the descriptors' bytes on the

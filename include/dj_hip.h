@@ -37,9 +37,10 @@ const char* dj_last_error(void);
 /* Version of this interface: bumped whenever an entry point is added or the meaning of an argument changes
  * (2: the `beta` / `relu` bit fields, the workspace and BatchNormalization-backward-statistics entry points, the per-thread
  * arithmetic mode; 3: storage-type codes for 16-bit tensors in HBM, the tuner direction 9; 4: one entry point per
- * convolution GEMM, taking an argument struct; their `_ws` / `_addrelu` / `_bn` / `_bnbwd` / `_relumask` / `_t` forms are gone).  A binding
+ * convolution GEMM, taking an argument struct; their `_ws` / `_addrelu` / `_bn` / `_bnbwd` / `_relumask` / `_t` forms are gone;
+ * 5: `dj_conv_fwd_args.bn` and `dj_bn_train` are gone).  A binding
  * written for one version must refuse a library that reports another (jpeg_detection_resnet_ssd_amd/_lib.py does). */
-#define DJ_ABI_VERSION 4
+#define DJ_ABI_VERSION 5
 int dj_abi_version(void);
 
 /* Storage type of a tensor in HBM, passed next to each ACTIVATION / GRADIENT tensor: the `dt_*` fields of the convolution
@@ -82,20 +83,6 @@ int dj_conv2d_fwd_stats_rows(const dj_conv2d_desc* d);
 #define DJ_CONV_Y_ZEROED 2        /* y is all zeros on entry: a split-K launch (atomic accumulation) does not clear it first */
 #define DJ_CONV_STATS_MAY_SPLIT 4 /* with `workspace`: a launch with `stats` is tuned like one without and may be split (its
                                    * statistics then come from the reduction); otherwise a launch with `stats` is never split */
-#define DJ_BN_ACC_REPLICAS 16
-typedef struct dj_bn_train {
-  double* acc;
-  unsigned* ticket;
-  const float* gamma;
-  const float* beta;
-  float* moving_mean; /* NULL: no moving-statistics update */
-  float* moving_var;
-  float* scale;
-  float* shift;
-  float* save_mean;
-  float* save_invstd;
-  float eps, momentum;
-} dj_bn_train;
 typedef struct dj_conv_fwd_args {
   /* operands: x fp32 | fp16; w the fp32 master weights or their fp16 shadow (dj_shadow_weights); y fp32 | fp16 (rounded
    * AFTER the fp32 bias / ReLU / statistics epilogue) */
@@ -139,14 +126,6 @@ typedef struct dj_conv_fwd_args {
    * split launch accumulates with fp32 atomics in arrival order. */
   float* workspace;
   long workspace_floats;
-  /* bn != NULL: convolution + the training-mode BatchNormalization that follows it (keras BatchNormalization(axis=3)
-   * after Conv2D, L/models/keras_ssd300_dct_j2d_resnet.py:66-99): the conv epilogue adds each tile's column sums / sums of
-   * squares to bn->acc with fp64 atomics, the workgroup that finishes last turns them into scale = gamma/sqrt(var+eps),
-   * shift = beta - mean*scale, save_mean / save_invstd (for the backward pass) and the momentum update of the moving
-   * statistics (Bessel-corrected variance), and leaves acc / ticket zero again.  Replaces `stats` +
-   * dj_bn_train_finalize: no launch between the conv and its consumer.  acc = DJ_BN_ACC_REPLICAS*2*out_c doubles and
-   * ticket = one unsigned, zero before the first launch.  fp32 tensors only; no `stats`, no DJ_CONV_RELU. */
-  const dj_bn_train* bn;
 } dj_conv_fwd_args;
 int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_args* a, void* stream);
 /* floats of workspace that make the CURRENT tuning choice for this geometry run without atomics (0: not split; < 0: bad

@@ -14,12 +14,6 @@ class DjError(RuntimeError):
     pass
 
 
-class BnTrain(Structure):   # dj_bn_train
-    _fields_ = [("acc", c_void_p), ("ticket", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
-                ("moving_mean", c_void_p), ("moving_var", c_void_p), ("scale", c_void_p), ("shift", c_void_p),
-                ("save_mean", c_void_p), ("save_invstd", c_void_p), ("eps", c_float), ("momentum", c_float)]
-
-
 class CopyPart(Structure):   # dj_copy_part
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("ld_src", c_long), ("ld_dst", c_long), ("rows", c_long),
                 ("cols", c_long), ("beta", c_int)]
@@ -76,7 +70,7 @@ class ConvFwdArgs(Structure):   # dj_conv_fwd_args: all zeros = fp32 tensors, no
     _fields_ = [("x", _P), ("dt_x", _I), ("w", _P), ("dt_w", _I), ("bias", _P), ("y", _P), ("dt_y", _I),
                 ("pro_scale", _P), ("pro_shift", _P), ("pro_relu", _I), ("flags", _I), ("stats", _P),
                 ("res", _P), ("ld_res", _I), ("res_scale", _P), ("res_shift", _P), ("sum_out", _P), ("ld_sum", _I),
-                ("dt_sum", _I), ("workspace", _P), ("workspace_floats", c_long), ("bn", POINTER(BnTrain))]
+                ("dt_sum", _I), ("workspace", _P), ("workspace_floats", c_long)]
 
 
 class ConvDgradArgs(Structure):   # dj_conv_dgrad_args
@@ -91,7 +85,7 @@ class ConvWgradArgs(Structure):   # dj_conv_wgrad_args
 
 
 _lib = None
-ABI_VERSION = 4     # DJ_ABI_VERSION of include/dj_hip.h these bindings were written for
+ABI_VERSION = 5    # DJ_ABI_VERSION of include/dj_hip.h these bindings were written for
 
 
 def load():

@@ -351,8 +351,7 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
   DJ_CHECK_ARG((a.dt_x == DJ_F32 || a.dt_x == DJ_F16) && (a.dt_y == DJ_F32 || a.dt_y == DJ_F16) &&
                    (dt_sum == DJ_F32 || dt_sum == DJ_F16) && (a.dt_w == DJ_F32 || a.dt_w == DJ_F16),
                "conv fwd: activations and the weight shadow are held as fp32 or fp16");
-  DJ_CHECK_ARG(!io16 || (dj_compute_mode() == 1 && !a.bn),
-               "conv fwd: 16-bit tensors need arithmetic mode 1 (float16) and no in-kernel BatchNormalization finalize");
+  DJ_CHECK_ARG(!io16 || dj_compute_mode() == 1, "conv fwd: 16-bit tensors need arithmetic mode 1 (float16)");
   DJ_CHECK_ARG((a.pro_scale == nullptr) == (a.pro_shift == nullptr), "conv fwd: pro_scale/pro_shift must come together");
   hipStream_t s = (hipStream_t)stream;
   float* const y = (float*)a.y;
@@ -381,7 +380,7 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
   p.ldc = d->ld_y;
   p.cmap = 0;
   const bool y_zeroed = (a.flags & DJ_CONV_Y_ZEROED) != 0;
-  const bool stats_may_split = (a.flags & DJ_CONV_STATS_MAY_SPLIT) != 0 && a.stats != nullptr && ws != nullptr && !a.bn;
+  const bool stats_may_split = (a.flags & DJ_CONV_STATS_MAY_SPLIT) != 0 && a.stats != nullptr && ws != nullptr;
   const int relu = a.flags & DJ_CONV_RELU;
   p.relu = relu;
   p.vecA = (d->in_c % 4 == 0) && (d->ld_x % 4 == 0) && aligned_dt(a.x, a.dt_x) &&
@@ -403,32 +402,9 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
   }
   p.b_bytes = extent_bytes((long)p.K, d->out_c, d->out_c, dt_size(a.dt_w));
   p.b_dt = a.dt_w;
-  if (a.bn) {
-    const dj_bn_train& b = *a.bn;
-    DJ_CHECK_ARG(b.acc && b.ticket && b.gamma && b.beta && b.scale && b.shift && b.save_mean && b.save_invstd,
-                 "conv fwd (BN): null pointer in dj_bn_train");
-    DJ_CHECK_ARG((b.moving_mean == nullptr) == (b.moving_var == nullptr), "conv fwd (BN): moving stats come together");
-    DJ_CHECK_ARG(a.stats == nullptr && !relu, "conv fwd (BN): no partial statistics / fused ReLU together with the fused finalize");
-    p.bn_acc = b.acc;
-    // one copy of the accumulators per 8192 GEMM rows: the big-M layers are the ones whose hundreds of workgroups
-    // would otherwise queue on the same 2*N addresses
-    p.bn_replicas = (int)std::min<long>(DJ_BN_ACC_REPLICAS, std::max<long>(1, p.M / 8192));
-    p.bn_ticket = b.ticket;
-    p.bn_gamma = b.gamma;
-    p.bn_beta = b.beta;
-    p.bn_moving_mean = b.moving_mean;
-    p.bn_moving_var = b.moving_var;
-    p.bn_scale = b.scale;
-    p.bn_shift = b.shift;
-    p.bn_save_mean = b.save_mean;
-    p.bn_save_invstd = b.save_invstd;
-    p.bn_eps = b.eps;
-    p.bn_momentum = b.momentum;
-    p.bn_count = (double)p.M;
-  }
   // statistics come out of the GEMM epilogue (one K range per tile) -- or, for a caller that allows it and supplies a
   // workspace, out of the slab reduction of a split launch (tuned like a launch without statistics)
-  const bool wants_stats = (a.stats != nullptr || a.bn != nullptr) && !stats_may_split;
+  const bool wants_stats = a.stats != nullptr && !stats_may_split;
   int splits = 1;
   int cfg = choose_cfg(p.M, p.N, p.K, !wants_stats, &splits);
   tune_lookup(wants_stats ? 4 : 0, d, &cfg, &splits);
@@ -436,7 +412,7 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
   if (a.dt_y != DJ_F32) splits = 1;   // a 16-bit result is written by one K range (no slabs, no atomics)
   splits = split_k(p.K, splits, &p.kchunk);
   // split-K through slabs in the caller's workspace + a fixed-order reduction (deterministic), when they fit
-  bool slabs = splits > 1 && ws != nullptr && !a.bn && (long)splits * p.M * p.N <= a.workspace_floats && aligned16(ws);
+  bool slabs = splits > 1 && ws != nullptr && (long)splits * p.M * p.N <= a.workspace_floats && aligned16(ws);
   if (splits > 1 && !slabs && stats_may_split)   // statistics cannot come from atomics: one K range after all
     splits = split_k(p.K, 1, &p.kchunk);
   if (slabs) {

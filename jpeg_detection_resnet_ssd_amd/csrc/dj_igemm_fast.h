@@ -60,7 +60,9 @@ __device__ __forceinline__ f32x4 dj_buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned o
 //      2 = the masked accumulate (DjIgemmParams::mask_x; input-gradient GEMM only): the store loops are replaced by twins that
 //      also load the ReLU mask (dj_store_full_tile_relumask) -- again an instantiation of its own, the others are untouched.
 template <int BM, int BN, int WM, int WN, int AM, int BMD, int PRO, int NSTAGE = 2, int KS = 1, int NP = 0, int EPI = 0>
-__global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmParams p) {
+__global__ __launch_bounds__(256 * KS)
+__attribute__((amdgpu_waves_per_eu(dj_min_waves(1, BM, BN, WM, WN, AM, BMD, PRO, NSTAGE, KS, NP, EPI))))
+void dj_igemm_fast_kernel(const DjIgemmParams p) {
   static_assert(EPI == 0 || (AM == 1 && BMD == 1), "BatchNormalization backward statistics: input-gradient GEMM only");
   static_assert(EPI != 2 || PRO == 0, "masked accumulate: the input-gradient GEMM has no prologue");
   static_assert(NP == 0 || (PRO != 3 && KS == 1), "NP: no residual-add prologue, no in-workgroup K split");
@@ -582,11 +584,7 @@ __global__ __launch_bounds__(256 * KS) void dj_igemm_fast_kernel(const DjIgemmPa
     }
     __syncthreads();
     if (kg == 1) {
-      if (p.stats || p.bn_acc) __syncthreads();   // matches the barrier of the statistics epilogue
-      if (p.bn_acc) {                              // ... and the two of the in-kernel BatchNormalization finalize
-        __syncthreads();
-        __syncthreads();
-      }
+      if (p.stats) __syncthreads();   // matches the barrier of the statistics epilogue
       return;
     }
 #pragma unroll

@@ -186,7 +186,9 @@ __device__ __forceinline__ void dj_split_store3(short* dst, f32x4 v, int lo_off)
 //     K-step the NP 0 weight gradient spends on addresses, a dozen of them quarter rate, load the vector pipe about as
 //     heavily as the MFMAs load the matrix pipe.  Instantiated for PREC 3 / 4 (dj_conv_launch_h16.h).
 template <int BM, int BN, int AM, int BMD, int PRO, int PREC, int BK = 32, int PF = 1, int EPI = 0, int AT = 0, int BT = 0, int NP = 0>
-__global__ __launch_bounds__(256) void dj_igemm_h16_kernel(const DjIgemmParams p) {
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(dj_min_waves(2, BM, BN, AM, BMD, PRO, PREC, BK, PF, EPI, AT, BT, NP))))
+void dj_igemm_h16_kernel(const DjIgemmParams p) {
   static_assert(NP == 0 || PRO != 3, "NP: not with the residual-add prologue (which keeps row indices of its own)");
   static_assert(NP != 2 || AM != 2, "NP 2 (per-tap offsets) is for the k-contiguous A operand");
   static_assert(NP != 3 || AM == 2, "NP 3 (pixel walk) is for the weight gradient's gathered operand");

@@ -243,6 +243,7 @@ def save_tune_db(path=None):
 class GradRef(object):
     """Gradient of a Value: a buffer, optionally to be masked by `mask_y > 0` by whoever reads it
     (lets Add+ReLU hand its upstream gradient to both branches without materialising the mask)."""
+    __slots__ = ("buf", "mask_y", "also", "bwd_partial", "premasked", "consumed", "alias_readers")
 
     def __init__(self, buf, mask_y=None, also=None):
         self.buf = buf
@@ -263,6 +264,12 @@ class GradRef(object):
 
 
 class Value(object):
+    """A tensor of the plan: a buffer, optionally read through a virtual affine (+ ReLU), plus the state the lowerings
+    keep on it.  Every attribute is declared here: a name that is not raises AttributeError where it is assigned."""
+    __slots__ = ("buf", "scale", "shift", "relu", "needs_grad", "name", "grad", "alias_of", "alias_view", "pad", "conv_stats",
+                 "relu_child", "bn", "bn_saved", "bn_parent", "bn_applies_mask", "_mat", "add_relu_first", "pending_add",
+                 "ready_event", "side_done", "constant")
+
     def __init__(self, buf, scale=None, shift=None, relu=False, needs_grad=False, name=""):
         self.buf = buf
         self.scale = scale
@@ -277,6 +284,15 @@ class Value(object):
         self.conv_stats = None    # (partial, nrows, conv_bias) when the producing conv took BN statistics
         self.relu_child = None    # Value created by Activation('relu') on a virtual affine
         self.bn = None            # BatchNormalization record that produced this virtual affine
+        self.bn_saved = None      # (mean, invstd) saved by a training BatchNormalization: a consumer conv may take its backward stats
+        self.bn_parent = None     # on the relu_child: the BatchNormalization Value it was made from
+        self.bn_applies_mask = False   # BatchNormalization output whose backward consumes GradRef.mask_y / .also (see Add)
+        self._mat = None          # buffer the virtual affine was written out to (layers._materialised, once per Value)
+        self.add_relu_first = None     # relu(Add) output: the layer whose input gradient is the last writer of its gradient
+        self.pending_add = None   # relu(Add) not computed yet: operands for the consumer conv that evaluates it in its prologue
+        self.ready_event = None   # event recorded where buf became final: side-stream readers wait for it (Plan.mark_ready)
+        self.side_done = None     # event recorded when the side-stream launches that wrote buf were issued (Plan.side_results)
+        self.constant = False     # filled once at plan build (anchor boxes): Reshape / Concatenate copy it then, not per step
 
     @property
     def is_affine(self):
@@ -463,12 +479,12 @@ class Plan(object):
     # the side stream behind an event recorded when its input became final (`mark_ready`), and whoever consumes its
     # results on the main stream waits for `side_done` first (`wait_side_inputs`, called for every layer).
     def forward_side_ok(self, v):
-        return (self.side_stream is not None and getattr(v, "ready_event", None) is not None
+        return (self.side_stream is not None and v.ready_event is not None
                 and os.environ.get("DJ_SIDE_HEADS", "1") != "0")
 
     def mark_ready(self, v):
         """Record, at this point of the forward list, an event that says `v.buf` is final."""
-        if self.side_stream is None or getattr(v, "ready_event", None) is not None:
+        if self.side_stream is None or v.ready_event is not None:
             return
         ev = torch.cuda.Event()
         v.ready_event = ev
@@ -500,7 +516,7 @@ class Plan(object):
     def wait_side_inputs(self, values):
         """Main stream: wait for side-stream producers of `values` (once per producer event)."""
         for v in values:
-            done = getattr(v, "side_done", None)
+            done = v.side_done
             if done is None or id(done) in self._side_joined:
                 continue
             self._side_joined[id(done)] = done
@@ -579,7 +595,6 @@ class Plan(object):
         lib = _lib.load()
         ncfg = lib.dj_conv2d_tune_configs()
         names = [n for n, _ in _lib.ConvDesc._fields_][:15]
-        done = 0
         grown = False
         # geometries one of whose launches cannot be split over K (masked accumulate): their shared entry stays unsplit
         unsplit = {(d,) + tuple(getattr(ds, n) for n in names) for d, ds, f in self.conv_calls if getattr(f, "no_split", False)}
@@ -644,12 +659,10 @@ class Plan(object):
                         best = (t, cfg, sp)
             check(lib.dj_conv2d_tune_set(direction, desc, best[1], best[2]), "tune_set")
             _TUNED[key] = best
-            done += 1
             if verbose:
                 import sys
                 print("tuned dir=%d %s -> cfg %d splits %d (%.3f ms; default cfg %d splits %d)"
                       % (direction, key[1:], best[1], best[2], best[0], c0.value, s0.value), file=sys.stderr)
-        return done
 
     def note_grad(self, spec):
         """Record that every launch writing `spec.grad` has been emitted (data-parallel bucketing)."""

@@ -200,7 +200,7 @@ def _materialised(v, who, plan=None, allow_pad=False):
     if plan is None:
         raise NotImplementedError("%s cannot consume a virtual BatchNormalization output" % who)
     src = v.alias_of if (v.alias_of is not None and v.pad is not None) else v   # ZeroPadding2D alias shares the data
-    if getattr(src, "_mat", None) is None:
+    if src._mat is None:
         rows, c, ld = rows_of(src.buf)
         y = plan.empty(*src.buf.shape)
         zbuf, sc, sh, relu = src.buf, src.scale, src.shift, int(src.relu)
@@ -260,8 +260,8 @@ def _bn_backward_fusable(plan, model, layer, x):
     extra vector work of the epilogue costs less than that)."""
     if os.environ.get("DJ_FUSE_BNBWD", "1") == "0" or not plan.training:
         return None
-    bnv = x if getattr(x, "bn_saved", None) is not None else getattr(x, "bn_parent", None)
-    if bnv is None or getattr(bnv, "bn_saved", None) is None or x.alias_of is not None or x.pad is not None:
+    bnv = x if x.bn_saved is not None else x.bn_parent
+    if bnv is None or bnv.bn_saved is None or x.alias_of is not None or x.pad is not None:
         return None
     if x is bnv and bnv.relu_child is not None:
         return None
@@ -279,7 +279,7 @@ def _relu_mask_in_dgrad(plan, layer, x, desc, dy, w_bwd, own_memset):
     ends whose gradient has later writers, split-K or strided input gradients, or 16-bit tensors."""
     if os.environ.get("DJ_MASK_IN_DGRAD", _MASK_IN_DGRAD_DEFAULT) == "0" or not plan.training:
         return None
-    if getattr(x, "add_relu_first", None) is not layer or x.alias_of is not None or x.pad is not None or x.is_affine:
+    if x.add_relu_first is not layer or x.alias_of is not None or x.pad is not None or x.is_affine:
         return None
     if own_memset or plan.store16 or plan.compute_mode in (1, 2):
         return None
@@ -343,7 +343,7 @@ class Conv2D(Layer):
         concatenated, zero-padded filter bank."""
         if os.environ.get("DJ_FUSE_HEADS", "1") == "0" or x.is_affine or x.pad is not None:
             return [self]
-        if getattr(x, "pending_add", None) is not None:
+        if x.pending_add is not None:
             return [self]
         sibs = []
         for lyr in model.consumers_of(self.inbound[0]):
@@ -483,7 +483,6 @@ class Conv2D(Layer):
                 model.weight_shadows(plan)
                 w_bwd = self.kernel.parambf
         pro = (x.scale, x.shift, x.relu) if x.is_affine else (None, None, False)
-        stats = fused_bn = None
         consumers = model.consumers_of(self.outbound[0])
         bn_consumer = (plan.training and not relu and len(consumers) == 1 and isinstance(consumers[0], BatchNormalization))
         # Fewer than two 64x64 output tiles per CU (the 5x5 / 10x10 stages at batch 32): such a GEMM only fills the chip
@@ -495,28 +494,14 @@ class Conv2D(Layer):
         tile_limit = int(os.environ.get("DJ_SPLIT_SMALL_BN_TILES", "512"))
         few_tiles = (-(-(b * desc.out_h * desc.out_w) // 64)) * (-(-self.filters // 64)) < tile_limit
         split_instead = bn_consumer and few_tiles and os.environ.get("DJ_SPLIT_SMALL_BN", "1") != "0"
-        if bn_consumer:
-            if os.environ.get("DJ_FUSE_BNFIN", "0") == "1" and not split_instead:
-                # opt-in: the conv's last workgroup turns the column sums into the BatchNormalization coefficients itself
-                # (fp64 accumulators + a ticket, both left zero by that workgroup).  Saves the finalize launch but every
-                # workgroup pays a ticket round trip: 0.6 % SLOWER on the SSD300 step, hence off
-                bnl, c = consumers[0], self.filters
-                fused_bn = dict(scale=plan.empty(c), shift=plan.empty(c), mean=plan.empty(c), invstd=plan.empty(c))
-                acc = torch.zeros(Kn.BN_ACC_REPLICAS * 2 * c, dtype=torch.float64, device=plan.device)
-                ticket = torch.zeros(1, dtype=torch.int32, device=plan.device)
-                bn_arg = Kn.make_bn_train(acc, ticket, bnl.gamma.param, bnl.beta.param, bnl.moving_mean.param,
-                                          bnl.moving_variance.param, fused_bn["scale"], fused_bn["shift"],
-                                          fused_bn["mean"], fused_bn["invstd"], bnl.epsilon, bnl.momentum)
-            else:
-                nrows = Kn.conv2d_stats_rows(desc)
-                stats = plan.empty(nrows, 2, self.filters)
+        stats = plan.empty(Kn.conv2d_stats_rows(desc), 2, self.filters) if bn_consumer else None
         # a split-K forward (the small-M layers) leaves its partial tiles in the plan's workspace and a fixed-order
         # reduction writes y (and takes the statistics of a `split_instead` launch): bit-reproducible, no cleared y
         # Raw output in fp16 (config 5 proper) when it feeds nothing but a BatchNormalization whose readers take 16-bit
         # tensors and this layer's own gradient GEMMs can read the bf16 gradient that comes back
         y_dtype = torch.float32
         if (plan.store16 and len(consumers) == 1 and isinstance(consumers[0], BatchNormalization) and not relu
-                and not split_instead and fused_bn is None and self.accepts16(cin)
+                and not split_instead and self.accepts16(cin)
                 and _takes16(model, consumers[0].outbound[0])):
             y_dtype = plan.act_dtype(b * desc.out_h * desc.out_w, self.filters)
         if x.buf.dtype != torch.float32 and not self.accepts16(cin):
@@ -524,30 +509,23 @@ class Conv2D(Layer):
         y = plan.empty(b, desc.out_h, desc.out_w, self.filters, dtype=y_dtype)
         ws = plan.conv_workspace(desc, stats_may_split=split_instead)
         xbuf = x.buf
-        pend = getattr(x, "pending_add", None)
+        pend = x.pending_add
         if pend is not None:
             # x = relu(bn(z) + shortcut) has not been computed yet: this conv evaluates it while staging its A tile and
             # writes it to xbuf for everybody else (Add.lower picked this layer because it runs first)
             assert pend["consumer"] is self, "a residual sum must be materialised by its first consumer"
             zb, zs, zt, rb, rs, rt = pend["z"], pend["z_scale"], pend["z_shift"], pend["res"], pend["res_scale"], pend["res_shift"]
-            if fused_bn is not None:
-                plan.emit_conv(4, desc, Kn.bound("conv2d_fwd_bn", desc, zb, wgt, bias, y, bn_arg, zs, zt, True, rb, rs, rt, xbuf))
-            else:
-                plan.emit_conv(4 if stats is not None else 0, desc,
-                               Kn.bound("conv2d_fwd_addrelu", desc, zb, w_fwd, bias, y, zs, zt, rb, rs, rt, xbuf, relu, stats,
-                                        ws=ws))
+            plan.emit_conv(4 if stats is not None else 0, desc,
+                           Kn.bound("conv2d_fwd_addrelu", desc, zb, w_fwd, bias, y, zs, zt, rb, rs, rt, xbuf, relu, stats, ws=ws))
             x.pending_add = None
             plan.mark_ready(x)     # the sum exists from here on: its other readers may run beside the main chain
-        elif fused_bn is not None:
-            plan.emit_conv(4, desc, Kn.bound("conv2d_fwd_bn", desc, xbuf, wgt, bias, y, bn_arg, pro[0], pro[1], pro[2]))
         else:
             plan.emit_conv(4 if (stats is not None and not split_instead) else 0, desc,
-                           Kn.bound("conv2d_fwd", desc, xbuf, w_fwd if fused_bn is None else wgt, bias, y, pro[0], pro[1], pro[2],
-                                    relu, stats, ws=ws, stats_may_split=split_instead))
+                           Kn.bound("conv2d_fwd", desc, xbuf, w_fwd, bias, y, pro[0], pro[1], pro[2], relu, stats, ws=ws,
+                                    stats_may_split=split_instead))
         out = Value(y, needs_grad=True, name=self.name)
         if stats is not None:
             out.conv_stats = (stats, stats.shape[0], bias)
-        out.bn_done = fused_bn
 
         def build_backward():
             if out.grad is None:
@@ -793,8 +771,7 @@ class BatchNormalization(Layer):
         x = ins[0]
         z = _materialised(x, self.name, plan)
         rows, c, ld = rows_of(z)
-        done = getattr(x, "bn_done", None) if plan.training else None
-        scale, shift = (done["scale"], done["shift"]) if done else (plan.empty(c), plan.empty(c))
+        scale, shift = plan.empty(c), plan.empty(c)
         gamma, beta = self.gamma.param, self.beta.param
         mm, mv = self.moving_mean.param, self.moving_variance.param
         out = Value(z, scale=scale, shift=shift, relu=False, needs_grad=True, name=self.name)
@@ -803,19 +780,16 @@ class BatchNormalization(Layer):
         if not plan.training:
             plan.emit(lambda: call("dj_bn_infer_coeffs", gamma, beta, mm, mv, self.epsilon, scale, shift, c))
             return out
-        if done:
-            mean, invstd = done["mean"], done["invstd"]   # written by the producing convolution's last workgroup
+        mean, invstd = plan.empty(c), plan.empty(c)
+        if x.conv_stats is not None:
+            partial, nrows, conv_bias = x.conv_stats
         else:
-            mean, invstd = plan.empty(c), plan.empty(c)
-            if x.conv_stats is not None:
-                partial, nrows, conv_bias = x.conv_stats
-            else:
-                assert z.dtype == torch.float32, "BatchNormalization statistics of a 16-bit tensor come from its producer"
-                nrows = query("dj_reduce_rows", rows)
-                partial, conv_bias = plan.empty(nrows, 2, c), None
-                plan.emit(lambda: call("dj_colstats_partial", z, rows, c, ld, partial))
-            plan.emit(launcher("dj_bn_train_finalize", partial, nrows, rows, conv_bias, gamma, beta, self.epsilon,
-                               self.momentum, mm, mv, scale, shift, mean, invstd, c))
+            assert z.dtype == torch.float32, "BatchNormalization statistics of a 16-bit tensor come from its producer"
+            nrows = query("dj_reduce_rows", rows)
+            partial, conv_bias = plan.empty(nrows, 2, c), None
+            plan.emit(lambda: call("dj_colstats_partial", z, rows, c, ld, partial))
+        plan.emit(launcher("dj_bn_train_finalize", partial, nrows, rows, conv_bias, gamma, beta, self.epsilon,
+                           self.momentum, mm, mv, scale, shift, mean, invstd, c))
         out.bn_saved = (mean, invstd)   # a consumer convolution may take this layer's backward statistics itself
 
         def build_backward():
@@ -837,7 +811,7 @@ class BatchNormalization(Layer):
             dgamma, dbeta = self.gamma.grad, self.beta.grad
             if dgamma is None:  # frozen layer: scratch
                 dgamma, dbeta = plan.empty(c), plan.empty(c)
-            fused = getattr(src.grad, "bwd_partial", None)
+            fused = src.grad.bwd_partial
             if fused is not None:
                 # the convolution that produced dy took the statistics in its epilogue (Conv2D.build_backward)
                 assert mode in (0, 2)
@@ -979,7 +953,7 @@ class Add(Layer):
             # identity block: the BatchNormalization branch applies the ReLU mask anyway (dj_bn_bwd_apply); it writes the
             # masked gradient for the identity shortcut in the same pass instead of a separate dj_relu_bwd sweep
             fuse = (relu_here and a.is_affine and a.needs_grad and not b.is_affine and b.needs_grad
-                    and getattr(a, "bn_applies_mask", False))
+                    and a.bn_applies_mask)
             readers, shared = [], False
             for v in (a, b):
                 if not v.needs_grad:
@@ -1056,7 +1030,7 @@ class Concatenate(Layer):
                 assert t.is_contiguous()
                 src, lds, rws = t, n, outer
             dst = yflat[:, off:off + n]
-            if getattr(v_of[id(t)], "constant", False):
+            if v_of[id(t)].constant:
                 # constant input (the anchor boxes): its slice of y is written once, now (not in a structure-only
                 # lowering on the host, which launches nothing)
                 if plan.device.type == "cuda":
@@ -1069,7 +1043,7 @@ class Concatenate(Layer):
         elif live_parts:
             plan.emit(engine.copy2d_multi(live_parts))     # one launch for all members
         out = Value(y, needs_grad=any(v.needs_grad for v in ins), name=self.name)
-        out.constant = all(getattr(v, "constant", False) for v in ins)
+        out.constant = all(v.constant for v in ins)
 
         def build_backward():
             if out.grad is None:
@@ -1125,7 +1099,7 @@ class Reshape(Layer):
         out = Value(xbuf.view(*shape), needs_grad=x.needs_grad, name=self.name)
         out.alias_of = x
         out.alias_view = lambda g: g.view(*shape)
-        out.constant = getattr(x, "constant", False)
+        out.constant = x.constant
         return out
 
 
@@ -1301,7 +1275,6 @@ class Dropout(Layer):
         forward.dj_entry = ("dj_dropout_fwd", self.name)      # structure checks find the launch by it
         plan.emit(forward)
         out = Value(y, needs_grad=x.needs_grad, name=self.name)
-        out.dropout = self
 
         def build_backward():
             if out.grad is None or not x.needs_grad:

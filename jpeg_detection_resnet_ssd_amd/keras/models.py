@@ -302,7 +302,7 @@ class Model(object):
             # a tensor with several readers may have some that only feed the end of the forward pass (SSD predictor
             # heads): note the point where it is final, so that they can run beside the main chain (Plan.emit_side)
             if (training and isinstance(out, Value) and len(self.consumers_of(lyr.outbound[0])) > 1
-                    and getattr(out, "pending_add", None) is None and getattr(out, "side_done", None) is None):
+                    and out.pending_add is None and out.side_done is None):
                 plan.mark_ready(out)
         # model inputs in the order given to Model(...)
         order = []
@@ -319,14 +319,9 @@ class Model(object):
         if training:
             plan.build_backward()
         if os.environ.get("DJ_AUTOTUNE", "1") != "0":
-            # timing an untuned geometry runs its launch, and a conv that finalizes its BatchNormalization advances
-            # that layer's moving statistics: put the non-trainable state back afterwards
-            state = self.flat_all[self._store["n_train"]:]
-            saved = state.clone()
-            if plan.autotune(reps=int(os.environ.get("DJ_AUTOTUNE_REPS", "2")),
-                             verbose=os.environ.get("DJ_AUTOTUNE_VERBOSE", "0") == "1",
-                             measure=os.environ.get("DJ_AUTOTUNE", "1") != "table"):
-                state.copy_(saved)
+            plan.autotune(reps=int(os.environ.get("DJ_AUTOTUNE_REPS", "2")),
+                          verbose=os.environ.get("DJ_AUTOTUNE_VERBOSE", "0") == "1",
+                          measure=os.environ.get("DJ_AUTOTUNE", "1") != "table")
             plan.finalize_workspaces()
             if os.environ.get("DJ_TUNE_SAVE"):
                 from ..engine import save_tune_db

@@ -32,7 +32,7 @@ class L2Normalization(Layer):
     def runs_beside(self, plan, model, ins):
         """Forward launch on the side stream (engine.Plan.emit_side) when every reader is a predictor head that runs there."""
         x = ins[0]
-        if not plan.forward_side_ok(x) or x.is_affine or getattr(x, "pending_add", None) is not None:
+        if not plan.forward_side_ok(x) or x.is_affine or x.pending_add is not None:
             return False
         users = model.consumers_of(self.outbound[0])
         from ..keras.layers import Conv2D

@@ -197,28 +197,6 @@ def conv2d_fwd_addrelu(desc, x, w, bias, y, pro_scale, pro_shift, res, res_scale
     return _fwd(_desc_for(desc, x, y), a, x, w, bias, y, pro_scale, pro_shift, stats, workspace)
 
 
-BN_ACC_REPLICAS = 16   # DJ_BN_ACC_REPLICAS of include/dj_hip.h
-
-
-def make_bn_train(acc, ticket, gamma, beta, moving_mean, moving_var, scale, shift, save_mean, save_invstd, eps, momentum):
-    """dj_bn_train descriptor (keeps the tensors alive through the returned object)."""
-    bn = _lib.BnTrain(ptr(acc), ptr(ticket), ptr(gamma), ptr(beta), ptr(moving_mean), ptr(moving_var), ptr(scale),
-                      ptr(shift), ptr(save_mean), ptr(save_invstd), float(eps), float(momentum))
-    bn._keep = (acc, ticket, gamma, beta, moving_mean, moving_var, scale, shift, save_mean, save_invstd)
-    return bn
-
-
-def conv2d_fwd_bn(desc, x, w, bias, y, bn, pro_scale=None, pro_shift=None, pro_relu=False, res=None, res_scale=None,
-                  res_shift=None, sum_out=None):
-    """Forward conv + the training-mode BatchNormalization statistics / coefficients of its output in one launch."""
-    import ctypes
-    assert not any16(x, w, y, res, sum_out), "conv2d_fwd_bn: the fused finalize is fp32 only, every tensor must be torch.float32"
-    a = _lib.ConvFwdArgs(pro_relu=int(pro_relu), bn=ctypes.pointer(bn))
-    if res is not None:
-        _residual(a, x, res, res_scale, res_shift, sum_out)
-    return _fwd(_desc_for(desc, x, y), a, x, w, bias, y, pro_scale, pro_shift, None, None)
-
-
 def _dgrad(desc, a, dy, w, bias, dx):
     d = _desc_for(desc, dx, dy)
     assert _weights_ok(w, d)

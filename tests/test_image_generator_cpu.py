@@ -433,7 +433,7 @@ def test_library_exports_the_entry_point_and_keeps_its_abi_version():
     from jpeg_detection_resnet_ssd_amd import _lib
     lib = _lib.load()
     assert "dj_rgb_warp" in _lib.SIGNATURES and hasattr(lib, "dj_rgb_warp")
-    assert lib.dj_abi_version() == _lib.ABI_VERSION == 4
+    assert lib.dj_abi_version() == _lib.ABI_VERSION == 5
 
 
 def _records(n=2):

@@ -276,7 +276,7 @@ def test_library_exports_the_entry_points_and_keeps_its_abi_version():
     lib = _lib.load()
     for name in ("dj_image_prep", "dj_image_prep_scratch_bytes"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.dj_abi_version() == 4
+    assert lib.dj_abi_version() == 5
 
 
 def _good_plan():

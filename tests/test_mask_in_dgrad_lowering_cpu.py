@@ -63,3 +63,23 @@ def test_a_masked_gradient_takes_no_further_writer():
         plan.grad_of(w)
     reader.consumed = True
     assert plan.grad_of(w)[1] == 1 and plan.grad_of(w)[0] is buf
+
+
+def test_lowering_state_of_values_and_gradrefs_is_declared():
+    """The lowerings keep their per-tensor state in declared attributes of Value / GradRef: a fresh Value reads the
+    neutral value for each (a fusion is off until a lowering switches it on) and a name that is not declared -- a
+    misspelt one would silently switch a fusion off -- raises where it is assigned."""
+    from jpeg_detection_resnet_ssd_amd.engine import GradRef, Value
+    v = Value(torch.zeros(1, 2, 2, 4), needs_grad=True, name="v")
+    for name in ("grad", "alias_of", "alias_view", "pad", "conv_stats", "relu_child", "bn", "bn_saved", "bn_parent", "_mat",
+                 "add_relu_first", "pending_add", "ready_event", "side_done"):
+        assert getattr(v, name) is None, name
+    for name in ("bn_applies_mask", "constant"):
+        assert getattr(v, name) is False, name
+    g = GradRef(v.buf)
+    assert g.mask_y is None and g.also is None and g.bwd_partial is None and g.alias_readers == ()
+    assert g.premasked is False and g.consumed is False
+    for obj in (v, g):
+        with pytest.raises(AttributeError):
+            obj.bn_svaed = (None, None)
+        assert not hasattr(obj, "__dict__")

@@ -386,7 +386,7 @@ def test_library_exports_the_entry_points_and_keeps_its_abi_version():
     lib = _built_lib()
     for name in ("dj_sgd_momentum_update", "dj_adam_update", "dj_adadelta_update", "dj_optim_groups_per_pass"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.dj_abi_version() == 4 and _lib.ABI_VERSION == 4
+    assert lib.dj_abi_version() == 5 and _lib.ABI_VERSION == 5
     assert lib.dj_optim_groups_per_pass() > 0 and lib.dj_optim_groups_per_pass() % 256 == 0
 
 

@@ -315,7 +315,7 @@ def test_library_exports_the_entry_point_and_keeps_its_abi_version():
     from jpeg_detection_resnet_ssd_amd import _lib
     lib = _lib.load()
     assert "dj_photometric" in _lib.SIGNATURES and hasattr(lib, "dj_photometric")
-    assert lib.dj_abi_version() == 4 and _lib.ABI_VERSION == 4
+    assert lib.dj_abi_version() == 5 and _lib.ABI_VERSION == 5
 
 
 def _call(lib, ops, **kw):

@@ -101,7 +101,7 @@ def test_library_exports_the_entry_point():
     from jpeg_detection_resnet_ssd_amd import _lib
     lib = _lib.load()
     assert "dj_rgb_to_dct" in _lib.SIGNATURES and hasattr(lib, "dj_rgb_to_dct")
-    assert lib.dj_abi_version() == 4
+    assert lib.dj_abi_version() == 5
 
 
 @pytest.mark.parametrize("kwargs, names", [

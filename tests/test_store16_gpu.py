@@ -209,8 +209,7 @@ def test_weight_gradient_with_16bit_tensors_every_variant(geom, x_dt, dy_dt, flo
 
 def test_typed_launches_are_refused_outside_their_domain(floatx):
     """A 16-bit tensor never goes through a silent conversion or the generic kernel: channel counts the branch-free
-    kernels cannot take, a strided 3x3 input gradient, the exact-fp32 mode and the fp32-only fused BatchNormalization finalize are
-    errors."""
+    kernels cannot take, a strided 3x3 input gradient and the exact-fp32 mode are errors."""
     from jpeg_detection_resnet_ssd_amd import _lib
     from jpeg_detection_resnet_ssd_amd import kernels as Kn
     x = torch.zeros(2, 8, 8, 24, dtype=F16, device="cuda")
@@ -231,14 +230,6 @@ def test_typed_launches_are_refused_outside_their_domain(floatx):
     y3 = torch.zeros(2, 8, 8, 64, device="cuda")
     with pytest.raises(_lib.DjError, match="mode 1"):
         Kn.conv2d_fwd(Kn.make_conv_desc(2, 8, 8, 64, 64, (1, 1)), x3, w3, None, y3)
-    # conv + BatchNormalization coefficients in one launch is fp32 only: the wrapper refuses a 16-bit x, y or residual operand
-    co = [torch.zeros(64, device="cuda") for _ in range(8)]
-    bn = Kn.make_bn_train(torch.zeros(Kn.BN_ACC_REPLICAS * 2 * 64, dtype=torch.float64, device="cuda"),
-                          torch.zeros(1, dtype=torch.int32, device="cuda"), *co, 1e-3, 0.99)
-    desc3 = Kn.make_conv_desc(2, 8, 8, 64, 64, (1, 1))
-    for x4, y4, res4 in ((x3, y3, None), (x3.float(), y3.to(F16), None), (x3.float(), y3, x3)):
-        with pytest.raises(AssertionError, match="torch.float32"):
-            Kn.conv2d_fwd_bn(desc3, x4, w3, None, y4, bn, res=res4)
     torch.cuda.synchronize()
 
 

@@ -13,6 +13,9 @@ without it, with `DJ_INDEX_FILE` in the same way, and yields synthetic batches o
 `--archi resnet_rgb` needs no index file: with `DJ_TRAIN_DIR` and `DJ_VAL_DIR` set it reads class sub-directories through
 keras.preprocessing.image.ImageDataGenerator exactly as classification_part/config/resnetRGB/config_file.py:157-172 does,
 and `DJ_DEVICE_PREP=1` moves the affine warp, the flips and `preprocess_input` of those images to the GPU.
+`DJ_DEVICE_DECODE=1` on top of `DJ_DEVICE_PREP=1` (an error without it) leaves the decoding of baseline JPEG files to the GPU
+as well, for every generator above: files travel as entropy-decoded coefficients, read on `DJ_DECODE_THREADS` host threads
+(default 16), and other files are decoded with Pillow as before (vgg_jpeg_keras/generators: `device_switches`).
 `prepare_horovod(hvd)` reproduces the reference's data-parallel scaling rules (:121-150) with `hvd` = the RCCL adapter
 of training.py."""
 from os import environ
@@ -28,6 +31,7 @@ from jpeg_detection_resnet_ssd_amd.keras.metrics import top_k_categorical_accura
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
 from jpeg_detection_resnet_ssd_amd.keras.utils import Sequence
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.evaluation import Evaluator
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import device_switches
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 
 
@@ -161,8 +165,7 @@ class TrainingConfiguration(object):
                                                                                  DCTGeneratorJPEG2DCTDeconv)
             cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
             self.validation_directory, self.index_file = directory, index_file
-            self._test_generator = cls(directory, index_file, self._batch_size, scale=False,
-                                       device_prep=environ.get("DJ_DEVICE_PREP", "0") == "1")
+            self._test_generator = cls(directory, index_file, self._batch_size, scale=False, **device_switches())
         elif self.archi == "resnet_rgb":
             self._test_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
         else:
@@ -178,8 +181,7 @@ class TrainingConfiguration(object):
                                      vertical_flip=True, validation_split=0, preprocessing_function=preprocess_input)
         else:
             gen = ImageDataGenerator(preprocessing_function=preprocess_input)
-        return gen.flow_from_directory(directory, target_size=self.img_size, batch_size=self.batch_size,
-                                       device_prep=environ.get("DJ_DEVICE_PREP", "0") == "1")
+        return gen.flow_from_directory(directory, target_size=self.img_size, batch_size=self.batch_size, **device_switches())
 
     def prepare_training_generators(self):
         rank = self.horovod.rank() if self.horovod is not None else 0
@@ -192,16 +194,16 @@ class TrainingConfiguration(object):
             from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (DCTGeneratorJPEG2DCT,
                                                                                  DCTGeneratorJPEG2DCTDeconv)
             cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
-            device_prep = environ.get("DJ_DEVICE_PREP", "0") == "1"
+            switches = device_switches()
             self.train_directory, self.validation_directory, self.index_file = real
             # as the reference (:166-172); its photometric `transformations` (:162) are opt-in: DJ_PHOTOMETRIC=1, on either path
             transformations = None
             if environ.get("DJ_PHOTOMETRIC", "0") == "1":
                 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import brightness, contrast, lighting, saturation
                 transformations = [lighting, contrast, brightness, saturation]
-            self._train_generator = cls(real[0], real[2], self._batch_size, scale=True, device_prep=device_prep,
-                                        transformations=transformations)
-            self._validation_generator = cls(real[1], real[2], self._batch_size, scale=False, device_prep=device_prep)
+            self._train_generator = cls(real[0], real[2], self._batch_size, scale=True, transformations=transformations,
+                                        **switches)
+            self._validation_generator = cls(real[1], real[2], self._batch_size, scale=False, **switches)
         elif self.archi == "resnet_rgb":
             self._train_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, seed=1000 * rank)
             self._validation_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)

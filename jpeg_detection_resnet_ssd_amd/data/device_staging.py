@@ -8,7 +8,8 @@ resize) share, none of which knows what a descriptor means:
     with `fill`, `views` and (in the subclass) `launch`; and, for the items of a batch that are `CoefficientImage`s
     (data/jpeg_pixels.py: a JPEG file's bytes in place of its decoded pixels), the decode descriptors, tables and raw
     coefficient planes that dj_jpeg_pixels turns into those items' staged pixels on the GPU;
-  * `ResidentBuffers`: the per-device buffers an emitter keeps and the staging, upload and launch of one plan (`run`);
+  * `StagingBuffers`: the per-device buffers kept across batches and the staging, upload and launch of one plan (`run`);
+    `ResidentBuffers`: the same with the JPEG settings of an emitter;
   * `run_once`: the same with fresh buffers, for callers outside `Model`.
 
 Pillow's `Image.resize` (src/libImaging/Resample.c) resamples in two passes, horizontal then vertical, each skipped when its
@@ -182,6 +183,21 @@ def check_images(images):
     if not images:
         raise ValueError("expected at least one image")
     return images
+
+
+def plan_items(images):
+    """What a plan takes per image: the `CoefficientImage` itself, (height, width) of a decoded array."""
+    return [im if isinstance(im, CoefficientImage) else im.shape[:2] for im in images]
+
+
+def item_shapes(items):
+    """(height, width) of every item of `plan_items`, as plain ints."""
+    return [(int(s.shape[0]), int(s.shape[1])) if isinstance(s, CoefficientImage) else (int(s[0]), int(s[1])) for s in items]
+
+
+def decoded(images):
+    """The batch with every `CoefficientImage` replaced by the host statement of its pixels."""
+    return [im.pixels() if isinstance(im, CoefficientImage) else im for im in images]
 
 
 def resize_host(image, size, resample=None, allowed=RESTATED):
@@ -387,20 +403,20 @@ def run_once(plan, images, device=None, out=None, stream=None, n_threads=None):
     return out
 
 
-class ResidentBuffers(object):
-    """An emitter's JPEG settings (`quality` / `tables` / `deconv` as for `DeviceDCTEmitter`) and its buffers, kept per
-    device and grown on demand: two pinned staging buffers used in turn, each refilled only after the upload that last
-    read it has finished (an event recorded behind the copy), the device copy of the staging buffer, the scratch of the
-    horizontal pass and the uint8 batch.  `n_threads`: host threads `StagedPlan.fill` reads coefficient planes with
-    (None: its default)."""
+class StagingBuffers(object):
+    """The buffers of whoever stages plans, kept per device and grown on demand: two pinned staging buffers used in turn,
+    each refilled only after the upload that last read it has finished (an event recorded behind the copy), the device
+    copy of the staging buffer, the scratch of the horizontal pass and the uint8 batch.  `n_threads`: host threads
+    `StagedPlan.fill` reads coefficient planes with (None: its default)."""
 
-    def __init__(self, quality=75, tables=None, deconv=False, n_threads=None):
-        from .jpeg_dct import resolve_tables
-        self.tables = resolve_tables(quality, tables)
-        self.quality = None if tables is not None else int(quality)
-        self.deconv = bool(deconv)
+    def __init__(self, n_threads=None):
         self.n_threads = None if n_threads is None else int(n_threads)
         self._state = {}
+
+    def blob(self, device):
+        """The device copy of the staging buffer that `run` uploaded last on `device`."""
+        import torch
+        return self._state[str(torch.device(device))]["blob"]
 
     @staticmethod
     def _grown(tensor, nbytes, device=None):
@@ -432,3 +448,14 @@ class ResidentBuffers(object):
         out = st["out"][:n_out].view(plan.out_shape)
         plan.launch(host, st["blob"], out, st["scratch"])
         return out
+
+
+class ResidentBuffers(StagingBuffers):
+    """An emitter's JPEG settings (`quality` / `tables` / `deconv` as for `DeviceDCTEmitter`) and its `StagingBuffers`."""
+
+    def __init__(self, quality=75, tables=None, deconv=False, n_threads=None):
+        from .jpeg_dct import resolve_tables
+        self.tables = resolve_tables(quality, tables)
+        self.quality = None if tables is not None else int(quality)
+        self.deconv = bool(deconv)
+        StagingBuffers.__init__(self, n_threads)

@@ -21,6 +21,7 @@ from . import device_staging as ds
 from .device_staging import (BICUBIC, BILINEAR, BOX, HAMMING, LANCZOS, NEAREST, PRECISION_BITS, check_image, check_images,  # noqa: F401
                              identity_coeffs, round_up)
 from .jpeg_dct import PendingInputs
+from .jpeg_pixels import CoefficientImage
 
 SUPPORTED = (BILINEAR, BICUBIC, BOX)      # NEAREST and LANCZOS stay refused here: the classifier generators never draw them
 
@@ -102,13 +103,17 @@ class BatchPlan(ds.StagedPlan):
     int32 pool of bounds and taps (one copy per distinct (source size, resized size) pair of the batch) and the layout of
     one staging buffer `[descriptors | pool | photometric lists | pixels]`, each part at a multiple of 64 bytes.  `ops`
     (optional): per image, the photometric operations [(code, parameters), ...] of data/photometric.py that
-    dj_photometric runs on the prepared pixels; without it the third part is empty."""
+    dj_photometric runs on the prepared pixels; without it the third part is empty.  An item of `shapes` may be a
+    `CoefficientImage` instead of (height, width): its whole image is then reconstructed on the GPU from the file's
+    coefficients into the place its pixels would have been copied to (`StagedPlan`), and the decode parts lie behind the
+    four above."""
     DESC_DTYPE = DESC_DTYPE
 
     def __init__(self, shapes, params, target_length=224, resample=None, ops=None):
         code = resolve_resample(resample)
         t = int(target_length)
-        shapes = [(int(h), int(w)) for h, w in shapes]
+        items = list(shapes)
+        shapes = ds.item_shapes(items)
         params = [(bool(s), int(o), bool(f)) for s, o, f in params]
         if len(shapes) != len(params) or not shapes:
             raise ValueError("expected one (scale, offset, flip) per image and at least one image")
@@ -139,12 +144,16 @@ class BatchPlan(ds.StagedPlan):
         if ops is not None:
             from .photometric import pack_ops
             self.ops = pack_ops(ops, self.batch)
-        self._lay_out([("desc", self.desc), ("pool", self.pool), ("ops", self.ops), ("src", self.src_bytes)])
+        # dj_image_prep reads any row of the source (its vertical taps reach where the resize puts them): the whole image is staged
+        decode = self._plan_decode(items, [(0, h, 0, w) for h, w in shapes],
+                                   [(int(d["src_offset"]), int(d["src_stride"])) for d in self.desc])
+        self._lay_out([("desc", self.desc), ("pool", self.pool), ("ops", self.ops), ("src", self.src_bytes)] + decode)
 
     def _fill_pixels(self, src, images):
         for d, (h, w), img in zip(self.desc, self.shapes, images):
-            o = int(d["src_offset"])
-            src[o:o + 3 * w * h].reshape(h, w, 3)[...] = img
+            if not isinstance(img, CoefficientImage):
+                o = int(d["src_offset"])
+                src[o:o + 3 * w * h].reshape(h, w, 3)[...] = img
 
     def launch_photometric(self, blob_dev, pixels, stream=None):
         """dj_photometric on the prepared batch, in place, its lists read from the device copy of the staging buffer."""
@@ -152,8 +161,10 @@ class BatchPlan(ds.StagedPlan):
         return kernels.photometric(pixels, self.part(blob_dev, self.ops_offset, self.ops), self.ops, stream=stream)
 
     def launch(self, blob_host, blob_dev, out, scratch, stream=None):
-        """dj_image_prep into `out`, then dj_photometric on it when the plan carries operation lists."""
+        """dj_jpeg_pixels for the items that travel as coefficients, dj_image_prep into `out`, then dj_photometric on it
+        when the plan carries operation lists."""
         from .. import kernels
+        self.launch_decode(blob_host, blob_dev, scratch, stream)
         src_h, desc_h, pool_h = self.views(blob_host)
         src_d, desc_d, pool_d = self.views(blob_dev)
         kernels.image_prep(src_d, desc_d, desc_h, pool_d, pool_h, self.target, out, scratch, stream=stream)
@@ -162,13 +173,16 @@ class BatchPlan(ds.StagedPlan):
         return out
 
 
-def prep_device(images, params, target_length=224, resample=None, device=None, out=None, stream=None, ops=None):
+def prep_device(images, params, target_length=224, resample=None, device=None, out=None, stream=None, ops=None,
+                n_threads=None):
     """`prep_host` for a list of (H_i, W_i, 3) uint8 images and per-image (scale, offset, flip) on the GPU -> the
     (B, target_length, target_length, 3) uint8 CUDA batch, for callers outside `Model` (fresh buffers every call;
-    `DeviceImagePrep` keeps its own).  `ops`: per-image photometric operation lists, run on the prepared pixels."""
+    `DeviceImagePrep` keeps its own).  `ops`: per-image photometric operation lists, run on the prepared pixels.  An
+    image may be a `CoefficientImage`: its pixels are then made on the GPU, its coefficients read by `n_threads` host
+    threads (`StagedPlan.fill`)."""
     images = check_images(images)
-    plan = BatchPlan([im.shape[:2] for im in images], params, target_length, resample, ops=ops)
-    return ds.run_once(plan, images, device, out, stream)
+    plan = BatchPlan(ds.plan_items(images), params, target_length, resample, ops=ops)
+    return ds.run_once(plan, images, device, out, stream, n_threads)
 
 
 class PendingImageInputs(PendingInputs):
@@ -187,7 +201,7 @@ class PendingImageInputs(PendingInputs):
             ops = check_ops(ops, len(self.images))
         self.ops = ops
         # descriptors and taps are made where the batch is made (a generator's prefetch thread), not at upload time
-        self.plan = BatchPlan([im.shape[:2] for im in self.images], self.params, prep.target_length, prep.resample, ops=ops)
+        self.plan = BatchPlan(ds.plan_items(self.images), self.params, prep.target_length, prep.resample, ops=ops)
         PendingInputs.__init__(self, prep, self.plan.out_shape)
 
     def sliced(self, index):
@@ -198,9 +212,11 @@ class PendingImageInputs(PendingInputs):
         return self.prep.run(self.plan, self.images, device)
 
     def pixels(self):
-        """The (B, T, T, 3) uint8 batch computed on the host (`prep_host` per image, then `photometric_host`)."""
+        """The (B, T, T, 3) uint8 batch computed on the host (`prep_host` per image, then `photometric_host`; an item that
+        travels as coefficients is `jpeg_pixels_host` of its file first)."""
         p = self.prep
-        out = np.stack([prep_host(im, p.target_length, s, o, f, p.resample) for im, (s, o, f) in zip(self.images, self.params)])
+        out = np.stack([prep_host(im, p.target_length, s, o, f, p.resample)
+                        for im, (s, o, f) in zip(ds.decoded(self.images), self.params)])
         if self.ops is not None:
             from .photometric import photometric_host
             out = photometric_host(out, self.ops)
@@ -213,15 +229,16 @@ class DeviceImagePrep(ds.ResidentBuffers):
     """Stands where the reference's classifier generators resize, crop and flip each decoded image in PIL and then save
     it as a JPEG and read it back (vgg_jpeg_keras/generators/generators.py:141-187): the generator thread only decodes
     and draws, the pixels go up once and both steps run on the GPU when the model uploads the batch.  `resample`: a
-    Pillow resampling code or name (None: Pillow's default, BICUBIC); `quality` / `tables` / `deconv` and the buffers as
-    `ResidentBuffers` keeps them."""
+    Pillow resampling code or name (None: Pillow's default, BICUBIC); `quality` / `tables` / `deconv`, `n_threads` and the
+    buffers as `ResidentBuffers` keeps them.  Handed `CoefficientImage`s, the generator thread does not even decode: the
+    files' coefficients go up and dj_jpeg_pixels makes the staged pixels."""
 
-    def __init__(self, target_length=224, resample=None, quality=75, tables=None, deconv=False):
+    def __init__(self, target_length=224, resample=None, quality=75, tables=None, deconv=False, n_threads=None):
         self.target_length = int(target_length)
         if self.target_length < 1:
             raise ValueError("target_length must be >= 1")
         self.resample = resolve_resample(resample)
-        ds.ResidentBuffers.__init__(self, quality, tables, deconv)
+        ds.ResidentBuffers.__init__(self, quality, tables, deconv, n_threads)
 
     def __call__(self, images, params, ops=None):
         return PendingImageInputs(self, images, params, ops)

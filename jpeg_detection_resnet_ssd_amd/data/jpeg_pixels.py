@@ -183,3 +183,17 @@ class CoefficientImage(object):
         """(3, 64) int32: the table of each component, natural order (gray: its one table three times)."""
         q = np.array(self.info.base.quant, dtype=np.int32)
         return q[:3].copy() if self.n_components == 3 else np.repeat(q[:1], 3, axis=0)
+
+
+def read_image(path):
+    """What a `device_decode` classifier generator hands over for the file at `path`: a `CoefficientImage` when the file
+    is `decodable`, else the (height, width, 3) uint8 array of Pillow's `convert("RGB")` (progressive or CMYK JPEG, PNG,
+    ...), decoded from the bytes already read."""
+    import io
+    with open(path, "rb") as f:
+        data = f.read()
+    if decodable(data):
+        return CoefficientImage(data)
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as image:
+        return np.array(image.convert("RGB"), dtype=np.uint8)

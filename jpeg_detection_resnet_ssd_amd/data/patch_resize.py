@@ -96,14 +96,14 @@ class PatchPlan(ds.StagedPlan):
     the staged rectangles before the resize; the records then travel as a fourth part behind the pixels.  Without them
     there is no such part and the layout is the three-part one.  An item of `shapes` may be a `CoefficientImage` instead of
     (height, width): its staged rectangle is then reconstructed on the GPU from the file's coefficients (`StagedPlan`),
-    whose parts lie behind all of these."""
+    whose parts lie behind all of these.  `extra`: further (name, array) parts a caller sends up in the same blob (the warp
+    records of data/rgb_warp.py), laid out behind the plan's own and before the decode parts."""
     DESC_DTYPE = DESC_DTYPE
     photo_offset = None
 
-    def __init__(self, shapes, geometries, out_height, out_width, photometric=None):
+    def __init__(self, shapes, geometries, out_height, out_width, photometric=None, extra=()):
         items = list(shapes)
-        shapes = [(int(s.shape[0]), int(s.shape[1])) if isinstance(s, CoefficientImage) else (int(s[0]), int(s[1]))
-                  for s in items]
+        shapes = ds.item_shapes(items)
         geometries = [check_geometry(g) for g in geometries]
         if len(shapes) != len(geometries) or not shapes:
             raise ValueError("expected one geometry per image and at least one image")
@@ -145,6 +145,7 @@ class PatchPlan(ds.StagedPlan):
                 raise ValueError("expected one photometric record per image: %d records for %d images"
                                  % (len(self.photo), self.batch))
             parts.append(("photo", self.photo))
+        parts += list(extra)
         parts += self._plan_decode(items, self.rects, [(int(d["src_offset"]), int(d["src_stride"])) for d in self.desc])
         self._lay_out(parts)
 
@@ -183,9 +184,7 @@ def patch_resize_device(images, geometries, out_height, out_width, device=None, 
     return ds.run_once(plan, images, device, out, stream)
 
 
-def _plan_items(images):
-    """What `PatchPlan` takes per image: the `CoefficientImage` itself, (height, width) of a decoded array."""
-    return [im if isinstance(im, CoefficientImage) else im.shape[:2] for im in images]
+_plan_items = ds.plan_items
 
 
 class PendingPatchInputs(PendingInputs):
@@ -221,7 +220,7 @@ class PendingPatchInputs(PendingInputs):
         records, then `patch_resize_host`, per image; an item that travels as coefficients is `jpeg_pixels_host` of its
         file first)."""
         p = self.prep
-        images = [im.pixels() if isinstance(im, CoefficientImage) else im for im in self.images]
+        images = ds.decoded(self.images)
         if self.photometric is not None:
             from .ssd_photometric import ssd_photometric_host
             images = [ssd_photometric_host(im, rec) for im, rec in zip(images, self.photometric)]

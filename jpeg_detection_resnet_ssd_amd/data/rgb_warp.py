@@ -13,7 +13,8 @@ What decides bits of the warp, all float64, each product and sum rounded once (n
     result = float32(out)
 
 `PendingRGBInputs` is one batch on its way into a model's resident input buffer through that kernel: the protocol of
-data/jpeg_dct.py:PendingInputs (`shape`, `shapes`, `sliced`, `emit_into`)."""
+data/jpeg_dct.py:PendingInputs (`shape`, `shapes`, `sliced`, `emit_into`).  `PendingRGBFileInputs` is the same batch one
+step earlier: files not yet decoded nor resized, which dj_jpeg_pixels and dj_patch_resize turn into that kernel's input."""
 import numpy as np
 
 PREP_NONE, PREP_CAFFE = 0, 1                          # DJ_RGB_PREP_* of include/dj_hip.h
@@ -209,3 +210,84 @@ class PendingRGBInputs(object):
     def numpy(self):
         """The same input computed on the host (`rgb_warp_host`), as the list of arrays the model takes."""
         return [rgb_warp_host(self.pixels, self.records, self.preprocess, self.rescale)]
+
+
+# ---- the same from files that are neither decoded nor resized on the host ----------------------------------------------------
+def load_geometry(height, width, resample):
+    """The `patch_resize` geometry of `load_img`'s resize: the whole image, no mirror, the iterator's filter.  Where a
+    side already has the target's length the plan takes the identity taps, so a file of the target size comes through
+    unchanged, as `load_img` leaves it."""
+    return (0, 0, int(height), int(width), False, resample, (0, 0, 0))
+
+
+class PendingRGBFileInputs(object):
+    """One batch of the RGB iterator whose files were neither decoded nor resized on the host: `images` holds a
+    `CoefficientImage` per file the GPU can reconstruct and the full-size (H_i, W_i, 3) uint8 array of every other,
+    `records` each image's drawn transform, `target_size` = (height, width) and `resample` the Pillow code of the
+    iterator's `interpolation`.  At upload time one pinned blob `[resize descriptors | taps | pixels of the decoded files |
+    warp records | decode descriptors | tables | coefficient planes]` goes up in one copy; dj_jpeg_pixels makes the
+    remaining pixels, dj_patch_resize (a whole-image window without mirror) the dense (B, H, W, 3) uint8 batch, and
+    dj_rgb_warp writes the model's input.  The protocol of `PendingRGBInputs`; `stager`: the `StagingBuffers` an iterator
+    keeps across batches."""
+
+    def __init__(self, images, records, target_size, resample, preprocess=PREP_NONE, rescale=None, stager=None):
+        from . import device_staging as ds
+        from .patch_resize import PatchPlan
+        self.images = ds.check_images(images)
+        height, width = (int(v) for v in target_size)
+        self.shape = (len(self.images), height, width, 3)
+        self.resample = ds.resolve_filter(resample)
+        records = np.ascontiguousarray(np.asarray(records))
+        if records.dtype != RECORD_DTYPE or records.shape != (len(self.images),):
+            raise ValueError("expected one RECORD_DTYPE record per image")
+        if preprocess not in (PREP_NONE, PREP_CAFFE):
+            raise ValueError("unknown preprocessing code %r" % (preprocess,))
+        self.records, self.preprocess = records, int(preprocess)
+        self.rescale = None if rescale is None else np.float32(rescale)
+        self.stager = stager if stager is not None else ds.StagingBuffers()
+        # descriptors and taps are made where the batch is made (the iterator's thread), not at upload time
+        self.plan = PatchPlan(ds.plan_items(self.images),
+                              [load_geometry(im.shape[0], im.shape[1], self.resample) for im in self.images],
+                              height, width, extra=[("records", self.records)])
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, index):
+        if not isinstance(index, slice):
+            raise TypeError("PendingRGBFileInputs can only be sliced along the batch")
+        return self.sliced(index)
+
+    def sliced(self, index):
+        return PendingRGBFileInputs(self.images[index], self.records[index], self.shape[1:3], self.resample,
+                                    self.preprocess, self.rescale, self.stager)
+
+    @property
+    def shapes(self):
+        return [self.shape]
+
+    def emit_into(self, buffers):
+        """Stage and upload the blob and launch dj_jpeg_pixels, dj_patch_resize and dj_rgb_warp on the current stream,
+        writing into `buffers[0]`: the float32 CUDA tensor of `self.shape`."""
+        buffers = list(buffers)
+        if [tuple(t.shape) for t in buffers] != self.shapes:
+            raise ValueError("emit_into: expected buffers of shapes %s, got %s"
+                             % (self.shapes, [tuple(t.shape) for t in buffers]))
+        from .. import kernels
+        device = buffers[0].device
+        pixels = self.stager.run(self.plan, self.images, device)
+        rec_dev = self.plan.part(self.stager.blob(device), self.plan.records_offset, self.records)
+        kernels.rgb_warp(pixels, rec_dev, self.records, buffers[0], self.preprocess,
+                         None if self.rescale is None else float(self.rescale))
+        return buffers
+
+    def pixels(self):
+        """The dense (B, H, W, 3) uint8 batch computed on the host: `CoefficientImage.pixels()` where a file travels as
+        coefficients, then `resize_host`."""
+        from . import device_staging as ds
+        size = (self.shape[2], self.shape[1])
+        return np.stack([ds.resize_host(im, size, self.resample) for im in ds.decoded(self.images)])
+
+    def numpy(self):
+        """The same input computed on the host (`pixels`, then `rgb_warp_host`), as the list of arrays the model takes."""
+        return [rgb_warp_host(self.pixels(), self.records, self.preprocess, self.rescale)]

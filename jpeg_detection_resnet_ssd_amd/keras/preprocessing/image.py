@@ -6,7 +6,8 @@ PARITY UNPINNED AGAINST keras_preprocessing; THE MODULE IS THE CONTRACT.  Keras-
 test compares with it.  What is pinned: the warp equals `scipy.ndimage.affine_transform(order=1, mode='nearest')` bit for
 bit (data/rgb_warp.py:affine_warp_host, tests/test_image_generator_cpu.py), the order of the `np.random` draws, the matrix
 composition and the standardisation are the rules written below, and the GPU path (csrc/dj_rgbwarp.hip, through
-`flow_from_directory(..., device_prep=True)`) equals the host path bit for bit.
+`flow_from_directory(..., device_prep=True)`) equals the host path bit for bit, and so does `device_decode=True` on top of it,
+which leaves JPEG decoding (csrc/dj_jpegpix.hip) and `load_img`'s resize (csrc/dj_patchresize.hip) to the GPU as well.
 
 Implemented arguments of `ImageDataGenerator`: rotation_range, width_shift_range / height_shift_range (float form),
 shear_range, zoom_range, horizontal_flip, vertical_flip, fill_mode='nearest', interpolation_order=1, rescale,
@@ -19,8 +20,8 @@ import warnings
 
 import numpy as np
 
-from ...data.rgb_warp import (PREP_CAFFE, PREP_NONE, PendingRGBInputs, RGBWarpStager, affine_warp_host, make_record,  # noqa: F401
-                              pack_records)
+from ...data.rgb_warp import (PREP_CAFFE, PREP_NONE, PendingRGBFileInputs, PendingRGBInputs, RGBWarpStager,  # noqa: F401
+                              affine_warp_host, make_record, pack_records)
 from ..utils import Sequence
 
 _PIL_INTERPOLATION_METHODS = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}
@@ -156,12 +157,12 @@ class ImageDataGenerator(object):
     def flow_from_directory(self, directory, target_size=(256, 256), color_mode="rgb", classes=None,
                             class_mode="categorical", batch_size=32, shuffle=True, seed=None, save_to_dir=None,
                             save_prefix="", save_format="png", follow_links=False, subset=None, interpolation="nearest",
-                            device_prep=False):
+                            device_prep=False, device_decode=False, decode_threads=None):
         return DirectoryIterator(directory, self, target_size=target_size, color_mode=color_mode, classes=classes,
                                  class_mode=class_mode, batch_size=batch_size, shuffle=shuffle, seed=seed,
                                  save_to_dir=save_to_dir, save_prefix=save_prefix, save_format=save_format,
                                  follow_links=follow_links, subset=subset, interpolation=interpolation,
-                                 device_prep=device_prep)
+                                 device_prep=device_prep, device_decode=device_decode, decode_threads=decode_threads)
 
     def flow(self, *args, **kwargs):
         raise NotImplementedError("ImageDataGenerator.flow is not implemented (only flow_from_directory)")
@@ -248,12 +249,17 @@ def _valid_files(directory, follow_links):
 class DirectoryIterator(Sequence):
     """Keras' DirectoryIterator: a `Sequence` (`len`, `[index]`, `on_epoch_end`) and an iterator (`next()`), yielding
     (float32 (b, H, W, 3), one-hot float32 labels) -- or, with `device_prep`, (PendingRGBInputs, labels): the same draws in
-    the same order, decode and resize on the host, warp, flips and standardisation on the GPU when the model uploads."""
+    the same order, decode and resize on the host, warp, flips and standardisation on the GPU when the model uploads.
+    With `device_decode` on top (ValueError without `device_prep`) the host neither decodes nor resizes: a file is read as
+    bytes, a baseline JPEG the GPU can reconstruct travels as a `CoefficientImage` and any other file as Pillow's full-size
+    RGB array, in a `PendingRGBFileInputs`; its coefficients are read on `decode_threads` host threads at upload time, and
+    dj_jpeg_pixels, `interpolation`'s resize (dj_patch_resize) and the warp run on the GPU.  `interpolation` must then be
+    a filter data/device_staging.py restates (every one but 'hamming': NotImplementedError)."""
 
     def __init__(self, directory, image_data_generator, target_size=(256, 256), color_mode="rgb", classes=None,
                  class_mode="categorical", batch_size=32, shuffle=True, seed=None, data_format="channels_last",
                  save_to_dir=None, save_prefix="", save_format="png", follow_links=False, subset=None,
-                 interpolation="nearest", dtype="float32", device_prep=False):
+                 interpolation="nearest", dtype="float32", device_prep=False, device_decode=False, decode_threads=None):
         if color_mode != "rgb":
             raise NotImplementedError("flow_from_directory: color_mode=%r is not implemented (only 'rgb')" % (color_mode,))
         if class_mode not in ("categorical", None):
@@ -272,14 +278,24 @@ class DirectoryIterator(Sequence):
         self.target_size = tuple(int(v) for v in target_size)
         self.image_shape = self.target_size + (3,)
         self.color_mode, self.class_mode, self.interpolation = color_mode, class_mode, interpolation
-        self.device_prep = bool(device_prep)
+        self.device_prep, self.device_decode = bool(device_prep), bool(device_decode)
+        if self.device_decode and not self.device_prep:
+            raise ValueError("device_decode needs device_prep: the coefficients are turned into pixels where the batch "
+                             "is staged for the GPU")
+        if self.device_decode:
+            from ...data import device_staging
+            self._resample = _PIL_INTERPOLATION_METHODS[interpolation]
+            if self._resample not in device_staging.RESTATED:
+                raise NotImplementedError("flow_from_directory(device_decode=True): interpolation=%r is not restated for "
+                                          "the device (only %s); use device_decode=False" % (interpolation, ", ".join(
+                                              k for k, v in _PIL_INTERPOLATION_METHODS.items() if v in device_staging.RESTATED)))
         if self.device_prep:
             fn = image_data_generator.preprocessing_function
             if fn is not None and getattr(fn, "_dj_device_prep", None) != PREP_CAFFE:
                 raise NotImplementedError("flow_from_directory(device_prep=True): preprocessing_function=%r cannot run on the "
                                           "device (only keras.applications.vgg16.preprocess_input or None)" % (fn,))
             self._prep_code = PREP_NONE if fn is None else PREP_CAFFE
-            self._stager = RGBWarpStager()
+            self._stager = device_staging.StagingBuffers(decode_threads) if self.device_decode else RGBWarpStager()
         if not classes:
             classes = sorted(d for d in os.listdir(directory) if os.path.isdir(os.path.join(directory, d)))
         self.num_classes = len(classes)
@@ -357,8 +373,23 @@ class DirectoryIterator(Sequence):
         y[np.arange(len(index_array)), self.classes[index_array]] = 1.
         return y
 
+    def _file_batch(self, index_array):
+        """The `device_decode` batch: the draws of the `device_prep` batch in the same order, no pixel touched."""
+        from ...data.jpeg_pixels import read_image
+        gen = self.image_data_generator
+        images, records = [], []
+        for j in index_array:
+            images.append(read_image(os.path.join(self.directory, self.filenames[j])))
+            records.append(gen.transform_record(self.image_shape, gen.get_random_transform(self.image_shape)))
+        gen._warn_unfit()      # the warning of the host path's `standardize`
+        return PendingRGBFileInputs(images, pack_records(records), self.target_size, self._resample, self._prep_code,
+                                    gen.rescale if gen.rescale else None, self._stager)
+
     def _get_batches_of_transformed_samples(self, index_array):
         gen = self.image_data_generator
+        if self.device_decode:
+            batch_x = self._file_batch(index_array)
+            return batch_x if self.class_mode is None else (batch_x, self._labels(index_array))
         if self.device_prep:
             pixels = np.empty((len(index_array),) + self.image_shape, dtype=np.uint8)
             records = []

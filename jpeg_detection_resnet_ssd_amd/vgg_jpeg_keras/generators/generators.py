@@ -10,7 +10,12 @@ decodes and draws: the batch is a `PendingImageInputs` and resize, crop, flip, t
 transform run on the GPU when the model uploads it (data/image_prep.py, csrc/dj_imgprep.hip, csrc/dj_photometric.hip),
 bit-exact with the host path.  On the device path `transformations` may hold only `saturation`, `brightness`, `contrast`
 and `lighting` of helper.py (recognised by identity): their draws from `np.random` are made here, in the host path's
-order, and travel with the batch.
+order, and travel with the batch.  `device_decode=True` on top of `device_prep=True` (ValueError without it) does not decode
+either: a file is read as bytes, and a baseline file the GPU can reconstruct (data/jpeg_pixels.py:`decodable`) travels as a
+`CoefficientImage` -- its size, which the draws need, is the header's; its coefficients are entropy-decoded into the staging
+blob on `decode_threads` host threads when the model uploads the batch, and dj_jpeg_pixels makes the pixels.  Any other file
+(progressive, CMYK, ...) is decoded by Pillow as before and goes into the same batch.  Draws, labels and the state of
+`random` / `np.random` after a batch are those of `device_prep=True`.
 
 Differences from the reference, all outside the numbers: class directories and files are listed in sorted order (the
 reference takes `os.listdir` order), inputs are float32 and labels float32 (the reference fills int32 arrays with the same
@@ -24,6 +29,7 @@ import numpy as np
 
 from ...data import image_prep
 from ...data.jpeg_dct import emit_dct_inputs
+from ...data.jpeg_pixels import read_image
 from ...keras.utils import Sequence
 from . import helper
 
@@ -41,12 +47,27 @@ def prepare_imagenet(index_file, data_directory):
     return association, classes, images_path
 
 
+def device_switches(environ=os.environ):
+    """The device arguments of the real-data generators (these and `flow_from_directory`) as the configurations read
+    them from the environment: `DJ_DEVICE_PREP=1`, `DJ_DEVICE_DECODE=1` on top of it (ValueError without it) and
+    `DJ_DECODE_THREADS`, default 16 and never derived from the CPU count."""
+    device_prep = environ.get("DJ_DEVICE_PREP", "0") == "1"
+    device_decode = environ.get("DJ_DEVICE_DECODE", "0") == "1"
+    if device_decode and not device_prep:
+        raise ValueError("DJ_DEVICE_DECODE=1 needs DJ_DEVICE_PREP=1")
+    return {"device_prep": device_prep, "device_decode": device_decode,
+            "decode_threads": int(environ.get("DJ_DECODE_THREADS", "16"))}
+
+
 class DCTGeneratorJPEG2DCT(Sequence):
     """Batches of `[X_y, X_cbcr]` ((B, T/8, T/8, 64), (B, T/16, T/16, 128)) and one-hot labels."""
     deconv = False
 
     def __init__(self, data_directory, index_file, batch_size=32, shuffle=True, scale=True, target_length=224, flip=True,
-                 transformations=None, device_prep=False, resample=None):
+                 transformations=None, device_prep=False, resample=None, device_decode=False, decode_threads=None):
+        if device_decode and not device_prep:
+            raise ValueError("device_decode needs device_prep: the coefficients are turned into pixels where the batch "
+                             "is staged for the GPU")
         if device_prep and transformations is not None and \
                 not all(helper.photometric_code(t) is not None for t in transformations):
             raise NotImplementedError(
@@ -65,11 +86,13 @@ class DCTGeneratorJPEG2DCT(Sequence):
         self.flip = flip
         self.transformations = transformations
         self.device_prep = bool(device_prep)
+        self.device_decode = bool(device_decode)
         self.resample = image_prep.resolve_resample(resample)
         self.number_of_classes = len(self.classes)
         self.batches_per_epoch = len(self.images_path) // self.batch_size
         self.indexes = np.arange(len(self.images_path))
-        self._prep = image_prep.DeviceImagePrep(target_length, self.resample, deconv=self.deconv) if device_prep else None
+        self._prep = image_prep.DeviceImagePrep(target_length, self.resample, deconv=self.deconv,
+                                                n_threads=decode_threads) if device_prep else None
         self.on_epoch_end()
 
     def __len__(self):
@@ -131,16 +154,20 @@ class DCTGeneratorJPEG2DCT(Sequence):
         images, params, ops = [], [], []
         for i, k in enumerate(indexes):
             path = self.images_path[k]
-            with Image.open(path) as im:
-                im = im.convert("RGB")
-                if self.device_prep:
-                    pixels = np.asarray(im)
-                    images.append(pixels)
-                    draws, image_ops = self._draws(pixels.shape[0], pixels.shape[1])
-                    params.append(draws)
-                    ops.append(image_ops)
+            if self.device_prep:
+                # a `CoefficientImage`'s shape is its header's: the draws need no pixels
+                if self.device_decode:
+                    pixels = read_image(path)
                 else:
-                    images.append(self._host_pixels(im))
+                    with Image.open(path) as im:
+                        pixels = np.asarray(im.convert("RGB"))
+                images.append(pixels)
+                draws, image_ops = self._draws(pixels.shape[0], pixels.shape[1])
+                params.append(draws)
+                ops.append(image_ops)
+            else:
+                with Image.open(path) as im:
+                    images.append(self._host_pixels(im.convert("RGB")))
             y[i, self._label(path)] = 1
         if self.device_prep:
             return self._prep(images, params, ops if self.transformations is not None else None), y

@@ -6,7 +6,9 @@ builder and the project name only, so each is a subclass that names them; a save
 
 Data: with `DJ_TRAIN_DIR`, `DJ_VAL_DIR` and `DJ_INDEX_FILE` all set, DCTGeneratorJPEG2DCT reads real images -- the training
 one with `scale=True` and the four photometric transformations when `DJ_PHOTOMETRIC=1`, the validation one with
-`scale=False`; `DJ_DEVICE_PREP=1` moves resize, crop, flip and the JPEG transform to the GPU.  Otherwise synthetic
+`scale=False`; `DJ_DEVICE_PREP=1` moves resize, crop, flip and the JPEG transform to the GPU, and `DJ_DEVICE_DECODE=1` on
+top of it (an error without it) the decoding of baseline JPEG files, read on `DJ_DECODE_THREADS` host threads (default 16).
+Otherwise synthetic
 [Y 28x28x64, CbCr 14x14x128] batches with one-hot labels.  `prepare_testing_generator` reads `DJ_TEST_DIR`, or `DJ_VAL_DIR`
 without it, with `DJ_INDEX_FILE`."""
 from os import environ
@@ -121,10 +123,10 @@ class VGGDCTTrainingConfiguration(object):
         directory = environ.get("DJ_TEST_DIR") or environ.get("DJ_VAL_DIR")
         index_file = environ.get("DJ_INDEX_FILE")
         if directory and index_file:
-            from .generators import DCTGeneratorJPEG2DCT
+            from .generators import DCTGeneratorJPEG2DCT, device_switches
             self.validation_directory, self.index_file = directory, index_file
             self._test_generator = DCTGeneratorJPEG2DCT(directory, index_file, self._batch_size, scale=False,
-                                                        device_prep=environ.get("DJ_DEVICE_PREP", "0") == "1")
+                                                        **device_switches())
         else:
             self._test_generator = SyntheticVGGDCTGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
 
@@ -132,17 +134,16 @@ class VGGDCTTrainingConfiguration(object):
         rank = self.horovod.rank() if self.horovod is not None else 0
         real = [environ.get(k) for k in ("DJ_TRAIN_DIR", "DJ_VAL_DIR", "DJ_INDEX_FILE")]
         if all(real):
-            from .generators import DCTGeneratorJPEG2DCT
-            device_prep = environ.get("DJ_DEVICE_PREP", "0") == "1"
+            from .generators import DCTGeneratorJPEG2DCT, device_switches
+            switches = device_switches()
             self.train_directory, self.validation_directory, self.index_file = real
             transformations = None
             if environ.get("DJ_PHOTOMETRIC", "0") == "1":
                 from .generators import brightness, contrast, lighting, saturation
                 transformations = [lighting, contrast, brightness, saturation]
             self._train_generator = DCTGeneratorJPEG2DCT(real[0], real[2], self._batch_size, scale=True,
-                                                         device_prep=device_prep, transformations=transformations)
-            self._validation_generator = DCTGeneratorJPEG2DCT(real[1], real[2], self._batch_size, scale=False,
-                                                              device_prep=device_prep)
+                                                         transformations=transformations, **switches)
+            self._validation_generator = DCTGeneratorJPEG2DCT(real[1], real[2], self._batch_size, scale=False, **switches)
         else:
             self._train_generator = SyntheticVGGDCTGenerator(self._batch_size, self.num_classes, seed=1000 * rank)
             self._validation_generator = SyntheticVGGDCTGenerator(self._batch_size, self.num_classes, n_batches=8,

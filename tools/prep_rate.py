@@ -10,11 +10,16 @@ tensors at 224x224, host path vs device path:
   (e) the photometric stage (saturation, brightness, contrast, lighting, each drawn with probability 1/2 per image in a
       shuffled order, as the generators do): the device path with dj_photometric between the two kernels, the kernel
       alone by events, and the four numpy callables on the 64 prepared images on 16 threads
+  (f) device decode: the same batch as JPEG files (quality 90; the other rows work on Pillow's pixels of these files).
+      Pillow's decode in one thread, which is what (b) leaves in the generator; in its place the headers
+      (`CoefficientImage`), `BatchPlan.fill` with the coefficient read on 16 threads and on 1, the upload of the larger
+      blob, dj_jpeg_pixels alone and in front of dj_image_prep by events, and the whole `emit_into`; outputs asserted
+      equal to (b)'s.  No target: the yardstick is row (b) of the same run
 
     python tools/prep_rate.py [--reps 20] [--fit-steps 40] [--no-fit]
 
-Medians over `reps` after warm-up; every timed window ends in a device synchronise.  (a) and the host half of (d) need
-PIL; without it they are reported as not measured.  Prints one JSON line at the end."""
+Medians over `reps` after warm-up; every timed window ends in a device synchronise.  (a), (f) and the host half of (d)
+need PIL; without it they are reported as not measured.  Prints one JSON line at the end."""
 import argparse
 import itertools
 import json
@@ -95,6 +100,64 @@ def make_ops(rng, n):
     return ops
 
 
+def as_files(images):
+    """-> (the images saved as JPEG at quality 90, Pillow's pixels of those files)."""
+    import io
+
+    from PIL import Image
+    files, decoded = [], []
+    for img in images:
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, "JPEG", quality=90)
+        files.append(buf.getvalue())
+        decoded.append(pillow_decode(files[-1]))
+    return files, decoded
+
+
+def pillow_decode(data):
+    import io
+
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def decode_rows(res, files, images, params, bufs, want, dev, reps):
+    """Row (f).  `want`: the tensors (b) wrote for the same batch."""
+    from jpeg_detection_resnet_ssd_amd.data.jpeg_pixels import CoefficientImage
+    res["pillow_decode_1_thread_ms"] = median_ms(lambda: [pillow_decode(f) for f in files], max(5, reps // 2))
+    res["decode_headers_ms"] = median_ms(lambda: [CoefficientImage(f) for f in files], reps)
+    items = [CoefficientImage(f) for f in files]
+    res["files_MB"] = sum(len(f) for f in files) / 1e6
+    preps = {n: image_prep.DeviceImagePrep(target_length=T, deconv=True, n_threads=n) for n in (16, 1)}
+    pending = preps[16](items, params)
+    plan = pending.plan
+    assert plan.decode_items == list(range(len(files))), "every file of the batch must travel as coefficients"
+    staging = torch.empty(plan.nbytes, dtype=torch.uint8).pin_memory()
+    host = staging.numpy()
+    for n in (16, 1):
+        res["decode_fill_%d_threads_ms" % n] = median_ms(lambda: plan.fill(host, items, n), reps)
+        res["device_decode_%d_threads_ms" % n] = median_ms(lambda: preps[n](items, params).emit_into(bufs), reps)
+    res["device_decode_emit_only_ms"] = median_ms(lambda: pending.emit_into(bufs), reps)
+    torch.cuda.synchronize()
+    res["device_decode_equals_device_prep"] = all(torch.equal(a, b) for a, b in zip(want, bufs))
+    assert res["device_decode_equals_device_prep"], "device decode and device prep disagree"
+    plain = image_prep.BatchPlan([im.shape[:2] for im in images], params, T)
+    plain_staging = np.empty(plain.nbytes, dtype=np.uint8)
+    res["prep_fill_ms"] = median_ms(lambda: plain.fill(plain_staging, images), reps)      # the pixel copy (b) makes instead
+    res["decode_upload_MB"] = plan.nbytes / 1e6
+    res["decode_upload_pinned_ms"] = median_ms(lambda: staging.to(dev, non_blocking=True), reps)
+    blob = staging.to(dev)
+    pixels = torch.empty(plan.out_shape, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
+    res["jpeg_pixels_ms"] = event_ms(lambda: plan.launch_decode(host, blob, scratch), max(50, reps))
+    res["jpeg_pixels_image_prep_ms"] = event_ms(lambda: plan.launch(host, blob, pixels, scratch), max(50, reps))
+    res["decode_plan_ms"] = median_ms(lambda: preps[16](items, params), reps)
+    # one batch from files to input tensors: what the generator does (decode or headers, plan) plus the emission
+    res["files_to_tensors_ms"] = {"device_prep": res["pillow_decode_1_thread_ms"][0] + res["device_ms"][0],
+                                  "device_decode": res["decode_headers_ms"][0] + res["device_decode_16_threads_ms"][0]}
+
+
 def pil_prep(img, scale, offset, flip):
     from PIL import Image
     im = Image.fromarray(img)
@@ -118,12 +181,16 @@ def main():
     B = 64
     rng = np.random.default_rng(0)
     batches = [make_batch(rng, B) for _ in range(2)]
-    images, params = batches[0]
     try:
         import PIL
         have_pil = PIL.__version__
     except ImportError:
         have_pil = False
+    files = None
+    if have_pil:          # every row works on the pixels of the JPEG files row (f) sends up undecoded
+        files, decoded = as_files(batches[0][0])
+        batches[0] = (decoded, batches[0][1])
+    images, params = batches[0]
     res = {"batch": B, "target": T, "reps": args.reps, "pil": have_pil,
            "source_MB": sum(im.nbytes for im in images) / 1e6}
     shapes = jpeg_dct.input_shapes(B, T, T, deconv=True)
@@ -150,6 +217,12 @@ def main():
     if have_pil:
         res["device_equals_host"] = all(torch.equal(a, b) for a, b in zip(want, bufs))
         res["host_over_device"] = res["host_ms"][0] / res["device_ms"][0]
+    # (f) device decode, next to (b)
+    if have_pil:
+        torch.cuda.synchronize()
+        decode_rows(res, files, images, params, bufs, [b.clone() for b in bufs], dev, args.reps)
+    else:
+        res["device_decode_16_threads_ms"] = "not measured (no PIL)"
     # (c) the two kernels alone, by events
     plan = pending.plan
     staging = torch.empty(plan.nbytes, dtype=torch.uint8).pin_memory()

@@ -8,11 +8,16 @@ shear_range=0.2, zoom_range=0.2, vertical_flip=True, preprocessing_function=prep
   (ii) device: flow_from_directory(..., device_prep=True)[k] (decode + resize + draws on the host), the upload of pixels
                and records from pinned memory, and dj_rgb_warp by device events around 50 back-to-back launches, with the
                bytes it moves over that time
+  (iii) device decode: flow_from_directory(..., device_prep=True, device_decode=True)[k] (files read, headers, draws and
+               the plan; nothing decoded or resized on the host), `fill` of the blob with the coefficient read on 16
+               threads and on 1, the upload of that blob, the kernels by device events (dj_jpeg_pixels + dj_patch_resize,
+               then dj_rgb_warp) and the whole `emit_into`; the output asserted equal to (ii)'s
 
     python tools/rgb_input_rate.py [--reps 5] [--dir DIRECTORY]
 
 Medians over `reps` after a warm-up; every timed window ends in a device synchronise where the device takes part.  There is
-no target: the device path is compared with the host path of the same run on the same machine.  Prints one JSON line."""
+no target: the device path is compared with the host path of the same run on the same machine, and device decode with the
+device path of the same run.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -67,6 +72,53 @@ def median_ms(fn, reps, warmup=1, sync=False):
     return statistics.median(out), min(out), max(out)
 
 
+def event_ms(fn, reps, inner=20):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    windows = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        windows.append(e0.elapsed_time(e1) / inner)
+    return statistics.median(windows), min(windows), max(windows)
+
+
+def decode_rows(res, iterator, want, dev, reps):
+    """Row (iii).  `want`: the tensor (ii) wrote for the same seed."""
+    from jpeg_detection_resnet_ssd_amd.data.jpeg_pixels import CoefficientImage
+    its = {n: iterator(True, device_decode=True, decode_threads=n) for n in (16, 1)}
+    res["decode_host_part_ms"] = median_ms(lambda: its[16][0], reps)          # read, headers, draws, records, plan
+    out = torch.empty((B, T, T, 3), dtype=torch.float32, device=dev)
+    pending = iterator(True, device_decode=True, decode_threads=16)[0][0]     # a fresh iterator: the same seed, the same draws
+    assert all(isinstance(im, CoefficientImage) for im in pending.images), "every file must travel as coefficients"
+    plan = pending.plan
+    staging = torch.empty(plan.nbytes, dtype=torch.uint8).pin_memory()
+    host = staging.numpy()
+    for n in (16, 1):
+        res["decode_fill_%d_threads_ms" % n] = median_ms(lambda: plan.fill(host, pending.images, n), max(10, reps), warmup=2)
+        res["decode_batch_%d_threads_ms" % n] = median_ms(lambda: its[n][0][0].emit_into([out]), reps, sync=True)
+    res["decode_emit_ms"] = median_ms(lambda: pending.emit_into([out]), max(20, reps), warmup=3, sync=True)
+    res["device_decode_equals_device_prep"] = bool(torch.equal(out, want))
+    assert res["device_decode_equals_device_prep"], "device decode and device prep disagree"
+    res["decode_upload_MB"] = plan.nbytes / 1e6
+    res["decode_upload_ms"] = median_ms(lambda: staging.to(dev, non_blocking=True), max(20, reps), warmup=3, sync=True)
+    blob = staging.to(dev)
+    pixels = torch.empty(plan.out_shape, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
+    rec_dev = plan.part(blob, plan.records_offset, pending.records)
+    res["decode_jpeg_pixels_ms"] = event_ms(lambda: plan.launch_decode(host, blob, scratch), max(5, reps))
+    res["decode_pixels_resize_ms"] = event_ms(lambda: plan.launch(host, blob, pixels, scratch), max(5, reps))
+    res["decode_kernels_ms"] = event_ms(lambda: (plan.launch(host, blob, pixels, scratch),
+                                                 kernels.rgb_warp(pixels, rec_dev, pending.records, out, pending.preprocess, None)),
+                                        max(5, reps))
+    res["device_batch_over_decode_batch"] = res["device_batch_ms"][0] / res["decode_batch_16_threads_ms"][0]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -82,9 +134,9 @@ def main():
     write_files(root, B, np.random.default_rng(0))
     res = {"batch": B, "target": T, "reps": args.reps}
 
-    def iterator(device_prep):
+    def iterator(device_prep, **kw):
         return ImageDataGenerator(**TRAIN_ARGS).flow_from_directory(root, target_size=(T, T), batch_size=B, seed=1,
-                                                                    device_prep=device_prep)
+                                                                    device_prep=device_prep, **kw)
     host_it, dev_it = iterator(False), iterator(True)
     # (i) the host path
     res["host_batch_ms"] = median_ms(lambda: host_it[0], args.reps)
@@ -113,6 +165,9 @@ def main():
     res["device_emit_ms"] = median_ms(lambda: pending.emit_into([out]), max(20, args.reps), warmup=3, sync=True)
     res["device_equals_host"] = bool(np.array_equal(out.cpu().numpy(), want))
     res["device_batch_ms"] = median_ms(lambda: dev_it[0][0].emit_into([out]), args.reps, sync=True)
+    pending.emit_into([out])
+    torch.cuda.synchronize()
+    decode_rows(res, iterator, out.clone(), dev, args.reps)
     stager = rgb_warp.RGBWarpStager()
     res["upload_ms"] = median_ms(lambda: stager.upload(pending.pixels, pending.records, dev), max(20, args.reps), warmup=3,
                                  sync=True)

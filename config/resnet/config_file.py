@@ -16,6 +16,9 @@ and `DJ_DEVICE_PREP=1` moves the affine warp, the flips and `preprocess_input` o
 `DJ_DEVICE_DECODE=1` on top of `DJ_DEVICE_PREP=1` (an error without it) leaves the decoding of baseline JPEG files to the GPU
 as well, for every generator above: files travel as entropy-decoded coefficients, read on `DJ_DECODE_THREADS` host threads
 (default 16), and other files are decoded with Pillow as before (vgg_jpeg_keras/generators: `device_switches`).
+`DJ_COEFFICIENT_INPUTS=1` (with none of the three switches above, else an error) feeds the DCT architectures pre-sized
+baseline 4:2:0 files as their OWN coefficients instead (vgg_jpeg_keras/generators/coefficient_generators.py): a random
+window of whole MCUs and a lossless mirror for training, the centred window for validation and test.
 `prepare_horovod(hvd)` reproduces the reference's data-parallel scaling rules (:121-150) with `hvd` = the RCCL adapter
 of training.py."""
 from os import environ
@@ -31,7 +34,7 @@ from jpeg_detection_resnet_ssd_amd.keras.metrics import top_k_categorical_accura
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
 from jpeg_detection_resnet_ssd_amd.keras.utils import Sequence
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.evaluation import Evaluator
-from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import device_switches
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import coefficient_switch, device_switches
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 
 
@@ -165,12 +168,24 @@ class TrainingConfiguration(object):
                                                                                  DCTGeneratorJPEG2DCTDeconv)
             cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
             self.validation_directory, self.index_file = directory, index_file
-            self._test_generator = cls(directory, index_file, self._batch_size, scale=False, **device_switches())
+            if coefficient_switch():
+                self._test_generator = self._coefficient_generator(directory, index_file, training=False)
+            else:
+                self._test_generator = cls(directory, index_file, self._batch_size, scale=False, **device_switches())
         elif self.archi == "resnet_rgb":
             self._test_generator = SyntheticRGBGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
         else:
             self._test_generator = SyntheticDCTClassificationGenerator(self._batch_size, self.deconv, self.num_classes,
                                                                        n_batches=8, seed=999983)
+
+    def _coefficient_generator(self, directory, index_file, training):
+        """`DJ_COEFFICIENT_INPUTS=1`: pre-sized files fed as their own coefficients -- a random window and mirror for
+        training, the centred window and no mirror for validation and test."""
+        from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (DCTGeneratorCoefficients,
+                                                                             DCTGeneratorCoefficientsDeconv)
+        cls = DCTGeneratorCoefficientsDeconv if self.deconv else DCTGeneratorCoefficients
+        return cls(directory, index_file, self._batch_size, target_length=self.img_size[0], random_crop=training,
+                   flip=training, decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")))
 
     def _rgb_generator(self, directory, training):
         """The reference's two calls for the RGB ResNet50 (classification_part/config/resnetRGB/config_file.py:157-172)."""
@@ -194,8 +209,12 @@ class TrainingConfiguration(object):
             from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (DCTGeneratorJPEG2DCT,
                                                                                  DCTGeneratorJPEG2DCTDeconv)
             cls = DCTGeneratorJPEG2DCTDeconv if self.deconv else DCTGeneratorJPEG2DCT
-            switches = device_switches()
             self.train_directory, self.validation_directory, self.index_file = real
+            if coefficient_switch():
+                self._train_generator = self._coefficient_generator(real[0], real[2], training=True)
+                self._validation_generator = self._coefficient_generator(real[1], real[2], training=False)
+                return
+            switches = device_switches()
             # as the reference (:166-172); its photometric `transformations` (:162) are opt-in: DJ_PHOTOMETRIC=1, on either path
             transformations = None
             if environ.get("DJ_PHOTOMETRIC", "0") == "1":

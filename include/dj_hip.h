@@ -619,6 +619,35 @@ int dj_jpeg_pixels(const unsigned char* coef, long coef_bytes, const dj_jpeg_pix
                    const dj_jpeg_pixels_desc* desc_host, int n, const int* tables, long table_ints, unsigned char* dst,
                    long dst_bytes, unsigned char* scratch, long scratch_bytes, void* stream);
 
+/* ---- The networks' DCT input tensors from the files' OWN coefficients: a window of each file's raw int16 planes (as
+ * dj_jpeg_read_raw_batch left them), de-quantised and optionally mirrored, scattered into the float32 inputs -- bit for bit
+ * what data/coefficient_inputs.py:coefficient_inputs_host states.  Each value is (float)(int16)(coefficient * table entry):
+ * the product in int32, wrapped to int16 as the host reader's emission does, then converted.  Image i fills output blocks
+ * [i][0..yh)[0..yw) of out_y from its luma blocks (by0[0] + r, bx0[0] + c) and [i][0..ch)[0..cw) of out_cb / out_cr from its
+ * chroma blocks (by0[c] + r, bx0[c] + c); with flip != 0 output block column j takes window column n_cols - 1 - j and every
+ * coefficient of odd horizontal frequency (natural index k with k & 1) is negated in int16 (jpegtran's lossless mirror).
+ * A one-component image fills out_cb and out_cr with zeros: EVERY element of the three outputs is written.  Block (r, c)
+ * of image i lies 64 floats at out + ((i * rows + r) * cols + c) * ld; ld_* >= 64 (Cb and Cr may be the two halves of one
+ * 128-channel tensor) and *_floats is what may be written from each pointer.  Component c's plane is blocks_h[c] x
+ * blocks_w[c] x 64 values in natural order at coef + coef_offset[c] (bytes, a multiple of 16; coef itself 16-byte aligned)
+ * and its table 64 ints at tables + table_offset + 64 c (tables 16-byte aligned, table_offset a multiple of 4).  An output
+ * whose pointer is 16-byte aligned and whose ld is a multiple of 4 is written with 16-byte stores, any other element by
+ * element.  coef / desc_dev / tables / out_* are DEVICE pointers, desc_host the HOST copy of the descriptors, read during
+ * the call only: every offset, grid, window, table offset and stride is checked against the sizes given before anything is
+ * launched, and an error launches nothing and writes nothing.  One launch, no synchronisation: capturable. ---- */
+typedef struct dj_jpeg_dct_desc {
+  long coef_offset[3];             /* bytes */
+  int blocks_h[3], blocks_w[3];    /* the file's block grids */
+  int by0[3], bx0[3];              /* window origin, in blocks */
+  int table_offset;                /* ints */
+  int n_components;                /* 1 (gray) or 3 (YCbCr, luma 2x2 over chroma) */
+  int flip;                        /* 0 or 1 */
+} dj_jpeg_dct_desc;
+int dj_jpeg_dct_inputs(const unsigned char* coef, long coef_bytes, const dj_jpeg_dct_desc* desc_dev,
+                       const dj_jpeg_dct_desc* desc_host, int n, const int* tables, long table_ints, int yh, int yw, int ch,
+                       int cw, float* out_y, long ld_y, long y_floats, float* out_cb, long ld_cb, long cb_floats,
+                       float* out_cr, long ld_cr, long cr_floats, void* stream);
+
 /* ---- Pascal-VOC evaluation (L/eval_utils/average_precision_evaluator.py:570-925): `Evaluator.match_predictions`,
  * `compute_precision_recall` and `compute_average_precisions(mode='sample')` with results equal bit for bit to the host
  * methods (float64, their operation order; eval_utils/device_matching.py packs the inputs and restates the segment-wise

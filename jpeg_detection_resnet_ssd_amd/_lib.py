@@ -42,6 +42,11 @@ class JpegPixelsDesc(Structure):   # dj_jpeg_pixels_desc
                 + [(n, c_int * 3) for n in ("blocks_h", "blocks_w", "by0", "by1", "bx0", "bx1")])
 
 
+class JpegDctDesc(Structure):   # dj_jpeg_dct_desc
+    _fields_ = ([("coef_offset", c_long * 3)] + [(n, c_int * 3) for n in ("blocks_h", "blocks_w", "by0", "bx0")]
+                + [(n, c_int) for n in ("table_offset", "n_components", "flip")])
+
+
 class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
@@ -201,6 +206,8 @@ SIGNATURES = {
     "dj_ssd_photometric": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dj_jpeg_pixels": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p,
                                c_long, c_void_p]),
+    "dj_jpeg_dct_inputs": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_int, c_int,
+                                   FP, c_long, c_long, FP, c_long, c_long, FP, c_long, c_long, c_void_p]),
     "dj_eval_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
                               c_void_p]),

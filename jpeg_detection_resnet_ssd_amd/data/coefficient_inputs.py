@@ -1,0 +1,257 @@
+"""The networks' DCT inputs from a JPEG file's OWN coefficients: for a file that already has the network's geometry (a
+dataset resized once, an evaluation set) decoding to pixels and re-encoding only rebuilds, with a generation loss, numbers
+the entropy decoder already had.  This module states in numpy what reaches the model instead (`coefficient_inputs_host`),
+and carries a batch to a model's resident input buffers, where csrc/dj_jpegdct.hip (`kernels.jpeg_dct_inputs`) writes the
+same numbers bit for bit (`PendingCoefficientInputs`, `DeviceCoefficientInputs`).
+
+Eligible files: what data/jpeg_pixels.py:`decodable` accepts (baseline / extended-sequential Huffman, 8 bits) AND either one
+component (gray) or three with luma sampled 2x2 over chroma (4:2:0), the layout of the networks' inputs.  Anything else is
+a ValueError that names the reason; there is no Pillow fallback, because this path has no pixels.
+
+Window: (y0, x0, h, w) in pixels.  y0 and x0 are multiples of 16 (one MCU); along each axis the extent is a multiple of 16
+or the window ends at the image's edge.  It yields the block grids `blocks_for(h, w)` of data/jpeg_dct.py -- luma
+ceil(h/8) x ceil(w/8) from block (y0/8, x0/8), chroma ceil(ceil(h/2)/8) x ceil(ceil(w/2)/8) from block (y0/16, x0/16) --
+which must lie inside the file's grids.  The default is the whole file: a 300x300 file gives (38, 38, 64) and
+(19, 19, 128 | 64), the SSD300's inputs.
+
+Value: float32(int16(coefficient * table entry)) -- the product in int32, truncated to int16 by two's-complement
+wrap-around, then converted -- which is what the host reader emits (csrc/dj_jpeg.cpp: Decoder::emit, "jpeg2dct stores
+shorts"); for a whole-file window the statement equals `emit_dct_inputs(None, jpeg_bytes=[...])` bit for bit.  A gray file
+gives its Y plane and all-zero chroma.
+
+Mirror: jpegtran's lossless horizontal flip, for windows with w % 16 == 0 only (then both grids mirror about the same
+axis).  Output block column j of a component takes window block column n_cols - 1 - j, and in natural order k = 8u + v every
+coefficient of odd v (k & 1) is negated: cos((2(7 - x) + 1) v pi / 16) = (-1)^v cos((2x + 1) v pi / 16).  The negation is
+applied to the int16 value, with int16's wrap-around (-(-32768) = -32768), before the conversion to float.
+
+All arithmetic here is int32 / int16."""
+import numpy as np
+
+from ..jpeg2dct import numpy as reader
+from . import device_staging as ds
+from .jpeg_dct import PendingInputs, blocks_for
+from .jpeg_pixels import CoefficientImage
+
+MCU = 16
+
+# dj_jpeg_dct_desc (include/dj_hip.h), C layout
+DESC_DTYPE = np.dtype([("coef_offset", np.int64, 3)] + [(n, np.int32, 3) for n in ("blocks_h", "blocks_w", "by0", "bx0")]
+                      + [(n, np.int32) for n in ("table_offset", "n_components", "flip")], align=True)
+
+
+def check_file(item):
+    """bytes or a `CoefficientImage` -> the `CoefficientImage` of an eligible file; ValueError naming the reason for any
+    other (progressive, CMYK, 12-bit: the reader's verdict; 4:4:4, 4:2:2: the sampling)."""
+    image = item if isinstance(item, CoefficientImage) else CoefficientImage(item)
+    if image.n_components == 3 and image.sampling != (2, 2):
+        raise ValueError("this JPEG's luma is sampled %d x %d over chroma: only 4:2:0 (2 x 2) and gray files carry the "
+                         "networks' block grids" % image.sampling)
+    return image
+
+
+def check_files(files):
+    images = [check_file(f) for f in files]
+    if not images:
+        raise ValueError("expected at least one file")
+    return images
+
+
+def check_window(image, window=None):
+    """None (the whole file) or (y0, x0, h, w) -> plain ints, checked against the module's rules and the file's grids."""
+    height, width = image.shape[:2]
+    if window is None:
+        window = (0, 0, height, width)
+    y0, x0, h, w = (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or y0 % MCU or x0 % MCU:
+        raise ValueError("window origin (%d, %d) must be non-negative multiples of %d" % (y0, x0, MCU))
+    if h < 1 or w < 1:
+        raise ValueError("window extent %d x %d must be positive" % (h, w))
+    for name, o, e, size in (("rows", y0, h, height), ("columns", x0, w, width)):
+        if e % MCU and o + e != size:
+            raise ValueError("window %s: an extent of %d from %d is neither a multiple of %d nor ends at the image's edge (%d)"
+                             % (name, e, o, MCU, size))
+    # luma, then chroma (Cr's grid is Cb's; a gray file has none to leave)
+    for c, ((bh, bw), (gh, gw), (by0, bx0)) in enumerate(zip(image.grids(), blocks_for(h, w), origins((y0, x0)))):
+        if by0 + gh > bh or bx0 + gw > bw:
+            raise ValueError("window (%d, %d, %d, %d): component %d: %d x %d blocks from (%d, %d) leave the file's grid of "
+                             "%d x %d" % (y0, x0, h, w, c, gh, gw, by0, bx0, bh, bw))
+    return y0, x0, h, w
+
+
+def check_batch(images, windows=None, flips=None):
+    """-> (windows, flips, (h, w)) of a batch: one window shape for all, origins and flips per image."""
+    n = len(images)
+    windows = [None] * n if windows is None else list(windows)
+    flips = [False] * n if flips is None else [bool(f) for f in flips]
+    if len(windows) != n or len(flips) != n:
+        raise ValueError("expected one window and one flip per file (%d), got %d and %d" % (n, len(windows), len(flips)))
+    windows = [check_window(im, win) for im, win in zip(images, windows)]
+    shapes = sorted({win[2:] for win in windows})
+    if len(shapes) != 1:
+        raise ValueError("mixed window shapes in one batch: %s" % shapes)
+    h, w = shapes[0]
+    if any(flips) and w % MCU:
+        raise ValueError("the mirror needs a window width that is a multiple of %d, got %d" % (MCU, w))
+    return windows, flips, (h, w)
+
+
+def origins(window):
+    """Block origins ((by0, bx0) of luma, of chroma) of a window."""
+    y0, x0 = window[:2]
+    return (y0 // 8, x0 // 8), (y0 // 16, x0 // 16)
+
+
+def raw_planes(image):
+    """The file's raw (not de-quantised) int16 planes [(blocks_h, blocks_w, 64)] per component, read as the staging
+    layer reads them (the batch reader refuses a truncated file, as Pillow does); ValueError for a file that fails."""
+    grids = image.grids()
+    sizes = [bh * bw * 64 for bh, bw in grids]
+    offsets, caps = np.zeros((1, 4), dtype=np.int64), np.zeros((1, 4), dtype=np.int64)
+    offsets[0, :len(sizes)] = 2 * np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    caps[0, :len(sizes)] = sizes
+    out = np.zeros(2 * sum(sizes), dtype=np.uint8)
+    if reader.read_raw_batch([image.data], out, offsets, caps, n_threads=1).any():
+        raise ValueError("the file could not be read: %s" % reader.last_error())
+    values = out.view(np.int16)
+    return [values[o // 2:o // 2 + s].reshape(bh, bw, 64) for o, s, (bh, bw) in zip(offsets[0], sizes, grids)]
+
+
+def dequantised(plane, table):
+    """(..., 64) raw int16 coefficients and a (64,) table -> int16: the int32 product wrapped to int16."""
+    return (np.asarray(plane).astype(np.int32) * np.asarray(table).astype(np.int32)).astype(np.int16)
+
+
+def mirrored(blocks):
+    """(..., cols, 64) int16 -> the lossless horizontal mirror: block columns reversed, odd-v coefficients negated in int16."""
+    out = np.array(np.asarray(blocks, dtype=np.int16)[..., ::-1, :])
+    out[..., 1::2] = (-out[..., 1::2].astype(np.int32)).astype(np.int16)
+    return out
+
+
+def window_blocks(plane, table, by0, bx0, rows, cols, flip=False):
+    """The statement for one component: blocks [by0, by0 + rows) x [bx0, bx0 + cols) of a raw plane -> (rows, cols, 64)
+    float32."""
+    plane = np.asarray(plane)
+    if by0 < 0 or bx0 < 0 or by0 + rows > plane.shape[0] or bx0 + cols > plane.shape[1]:
+        raise ValueError("%d x %d blocks from (%d, %d) leave the plane of %d x %d" % ((rows, cols, by0, bx0) + plane.shape[:2]))
+    v = dequantised(plane[by0:by0 + rows, bx0:bx0 + cols], table)
+    return (mirrored(v) if flip else v).astype(np.float32)
+
+
+def coefficient_inputs_host(files, windows=None, flips=None, deconv=False):
+    """files: JPEG bytes or `CoefficientImage`s; windows: per file None or (y0, x0, h, w), one shape for the batch; flips:
+    per file -> `[X_y, X_cbcr]`, or `[X_y, X_cb, X_cr]` when deconv=True, float32."""
+    images = check_files(files)
+    windows, flips, (h, w) = check_batch(images, windows, flips)
+    (yh, yw), (ch, cw) = blocks_for(h, w)
+    n = len(images)
+    y, cb, cr = (np.zeros((n, yh, yw, 64), np.float32), np.zeros((n, ch, cw, 64), np.float32),
+                 np.zeros((n, ch, cw, 64), np.float32))
+    for i, (im, win, flip) in enumerate(zip(images, windows, flips)):
+        planes, tables = raw_planes(im), im.tables()
+        (ly, lx), (cy, cx) = origins(win)
+        y[i] = window_blocks(planes[0], tables[0], ly, lx, yh, yw, flip)
+        if im.n_components == 3:
+            cb[i] = window_blocks(planes[1], tables[1], cy, cx, ch, cw, flip)
+            cr[i] = window_blocks(planes[2], tables[2], cy, cx, ch, cw, flip)
+    return [y, cb, cr] if deconv else [y, np.concatenate([cb, cr], axis=-1)]
+
+
+# ---- the same numbers on the GPU ---------------------------------------------------------------------------------------------
+class CoefficientPlan(ds.StagedPlan):
+    """Descriptors, tables and the layout of one staging blob `[descriptors | tables | coefficient planes]`, every part
+    and every plane at a multiple of 64 bytes.  Whole planes are staged, because the batch reader emits whole planes;
+    the kernel reads only the window.  There are no pixels: nothing is staged but what the reader writes."""
+    DESC_DTYPE = DESC_DTYPE
+    scratch_bytes = 0
+    out_shape = (0,)
+
+    def __init__(self, images, windows, flips, grids):
+        n = len(images)
+        self.batch, self.grids = n, grids
+        self.desc = np.zeros(n, dtype=DESC_DTYPE)
+        self.tables = np.zeros((n, 3, 64), dtype=np.int32)
+        self.plane_offsets = np.zeros((n, 4), dtype=np.int64)      # relative to the "coef" part
+        self.plane_capacity = np.zeros((n, 4), dtype=np.int64)
+        coef_off = 0
+        for i, (im, win, flip) in enumerate(zip(images, windows, flips)):
+            d = self.desc[i]
+            d["table_offset"], d["n_components"], d["flip"] = 192 * i, im.n_components, int(flip)
+            self.tables[i] = im.tables()
+            luma, chroma = origins(win)
+            for c, (bh, bw) in enumerate(im.grids()):
+                d["blocks_h"][c], d["blocks_w"][c] = bh, bw
+                d["by0"][c], d["bx0"][c] = luma if c == 0 else chroma
+                d["coef_offset"][c] = coef_off
+                self.plane_offsets[i, c], self.plane_capacity[i, c] = coef_off, bh * bw * 64
+                coef_off += ds.round_up(bh * bw * 128)
+        self.coef_bytes = coef_off
+        self._lay_out([("desc", self.desc), ("tables", self.tables), ("coef", self.coef_bytes)])
+
+    def fill(self, staging, images, n_threads=None):
+        """Write descriptors and tables into `staging`, a uint8 numpy array of at least `nbytes`, and have `n_threads`
+        host threads (None: one per CPU this process may use, 16 at the most) entropy-decode the files' raw planes into
+        it; a file that fails there raises ValueError naming its index."""
+        for offset, content in self.parts:
+            staging[offset:offset + content.size] = content
+        self._read_planes(staging, images, list(range(self.batch)), n_threads)
+
+    def views(self, blob):
+        """(descriptors, tables, coefficient planes) of a staging buffer (numpy: a DESC_DTYPE array, int32, bytes) or of
+        its device copy (torch: bytes all three)."""
+        desc = self.part(blob, self.desc_offset, self.desc, DESC_DTYPE)
+        tables = self.part(blob, self.tables_offset, self.tables, np.int32)
+        return desc, tables, blob[self.coef_offset:self.coef_offset + self.coef_bytes]
+
+    def launch(self, blob_host, blob_dev, out, scratch=None, stream=None):
+        """dj_jpeg_dct_inputs into `out` = [Y, CbCr] or [Y, Cb, Cr]: float32 CUDA tensors of the batch's shapes."""
+        from .. import kernels
+        desc_h, tables_h, _ = self.views(blob_host)
+        desc_d, tables_d, coef_d = self.views(blob_dev)
+        outs = tuple(out) if len(out) == 3 else (out[0], out[1][..., :64], out[1][..., 64:])
+        kernels.jpeg_dct_inputs(coef_d, desc_d, desc_h, tables_d, tables_h, outs, stream=stream)
+        return out
+
+
+class PendingCoefficientInputs(PendingInputs):
+    """The files of one batch with their windows and mirrors, on their way into a model's resident input buffers
+    (`Model.train_on_batch / predict / fit_generator` accept it where they accept the list of input arrays): at upload time
+    the files' raw planes are entropy-decoded into pinned memory, one copy takes `[descriptors | tables | planes]` up
+    and one launch of dj_jpeg_dct_inputs writes the inputs.  `shape` is that of the pixel batch the windows stand for."""
+
+    def __init__(self, emitter, files, windows=None, flips=None):
+        self.images = check_files(files)
+        self.windows, self.flips, (h, w) = check_batch(self.images, windows, flips)
+        # descriptors and layout are made where the batch is made (a generator's prefetch thread), not at upload time
+        self.plan = CoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w))
+        PendingInputs.__init__(self, emitter, (len(self.images), h, w, 3))
+
+    def sliced(self, index):
+        return PendingCoefficientInputs(self.emitter, self.images[index], self.windows[index], self.flips[index])
+
+    def emit_into(self, buffers):
+        """One copy and one launch on the current stream, writing every element of `buffers`: float32 CUDA tensors of
+        `self.shapes` ([Y, CbCr] or [Y, Cb, Cr])."""
+        buffers = list(buffers)
+        if [tuple(t.shape) for t in buffers] != [tuple(s) for s in self.shapes]:
+            raise ValueError("emit_into: expected buffers of shapes %s, got %s"
+                             % (self.shapes, [tuple(t.shape) for t in buffers]))
+        return self.emitter.run(self.plan, self.images, buffers[0].device, out=buffers)
+
+    def numpy(self):
+        """The same inputs computed on the host: the statement."""
+        return coefficient_inputs_host(self.images, self.windows, self.flips, self.emitter.deconv)
+
+
+class DeviceCoefficientInputs(ds.StagingBuffers):
+    """Stands where a generator would decode a pre-sized file, crop it and encode it again: the generator thread reads
+    bytes and headers and draws, and the file's own coefficients reach the model's inputs through the `StagingBuffers` kept
+    here (two pinned buffers used in turn, the event behind the copy, the device blob grown on demand).  `n_threads`: host
+    threads that entropy-decode a batch (None: `StagedPlan.fill`'s default)."""
+
+    def __init__(self, deconv=False, n_threads=None):
+        self.deconv = bool(deconv)
+        ds.StagingBuffers.__init__(self, n_threads)
+
+    def __call__(self, files, windows=None, flips=None):
+        return PendingCoefficientInputs(self, files, windows, flips)

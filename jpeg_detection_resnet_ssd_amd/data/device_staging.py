@@ -352,13 +352,19 @@ class StagedPlan(object):
             staging[offset:offset + content.size] = content
         self._fill_pixels(staging[self.src_offset:self.src_offset + self.src_bytes], images)
         if self.decode is not None:
-            from ..jpeg2dct import numpy as reader
-            status = reader.read_raw_batch([images[i].data for i in self.decode_items], staging[:self.nbytes],
-                                           self.plane_offsets + self.coef_offset, self.plane_capacity,
-                                           n_threads if n_threads is not None else min(reader.default_threads(), MAX_FILL_THREADS))
-            if status.any():
-                raise ValueError("items %s of the batch could not be read: %s"
-                                 % ([self.decode_items[j] for j in np.flatnonzero(status)], reader.last_error()))
+            self._read_planes(staging, images, self.decode_items, n_threads)
+
+    def _read_planes(self, staging, images, items, n_threads=None):
+        """Entropy-decode the raw coefficient planes of `images[i]` for i in `items` into the "coef" part of `staging`,
+        where `plane_offsets` / `plane_capacity` say, on `n_threads` host threads (None: one per CPU this process may use,
+        16 at the most); ValueError naming the items that failed."""
+        from ..jpeg2dct import numpy as reader
+        status = reader.read_raw_batch([images[i].data for i in items], staging[:self.nbytes],
+                                       self.plane_offsets + self.coef_offset, self.plane_capacity,
+                                       n_threads if n_threads is not None else min(reader.default_threads(), MAX_FILL_THREADS))
+        if status.any():
+            raise ValueError("items %s of the batch could not be read: %s"
+                             % ([items[j] for j in np.flatnonzero(status)], reader.last_error()))
 
     def part(self, blob, offset, array, dtype=None):
         """The bytes of `array`'s part at `offset` of a staging buffer (a uint8 numpy array: viewed as `dtype`) or of its
@@ -424,9 +430,10 @@ class StagingBuffers(object):
             return _uint8(max(nbytes, 0 if tensor is None else tensor.numel() * 3 // 2), device)
         return tensor
 
-    def run(self, plan, images, device):
+    def run(self, plan, images, device, out=None):
         """Stage, upload and launch `plan` on the current stream -> the resident uint8 batch of `plan.out_shape` (valid
-        until the next call on this device)."""
+        until the next call on this device).  `out`: what the plan's `launch` writes instead of that batch (a plan whose
+        kernels write a model's input buffers themselves); it is returned."""
         import torch
         device = torch.device(device)
         st = self._state.setdefault(str(device), {"slots": [[None, None], [None, None]], "turn": 0, "blob": None,
@@ -445,7 +452,8 @@ class StagingBuffers(object):
         if slot[1] is None:
             slot[1] = torch.cuda.Event()
         slot[1].record()
-        out = st["out"][:n_out].view(plan.out_shape)
+        if out is None:
+            out = st["out"][:n_out].view(plan.out_shape)
         plan.launch(host, st["blob"], out, st["scratch"])
         return out
 

@@ -516,6 +516,45 @@ def jpeg_pixels(coef, desc_dev, desc_host, tables_dev, tables_host, dst, scratch
     return dst
 
 
+# ---- the DCT input tensors from the files' own coefficients: window, mirror, de-quantise, scatter ----------------------------
+def _block_stride(t, name, n, rows, cols):
+    """(floats between the blocks of a (n, rows, cols, 64) float32 view, floats that may be written from its first
+    element): blocks equally spaced in (image, row, column) order, 64 contiguous floats each."""
+    assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (n, rows, cols, 64), \
+        "%s: expected float32 %s, got %s %s" % (name, (n, rows, cols, 64), t.dtype, tuple(t.shape))
+    ld = t.stride(2) if cols > 1 else (t.stride(1) if rows > 1 else (t.stride(0) if n > 1 else 64))
+    assert t.stride(3) == 1 and ld >= 64 and (cols == 1 or t.stride(2) == ld) and (rows == 1 or t.stride(1) == cols * ld) \
+        and (n == 1 or t.stride(0) == rows * cols * ld), "%s: blocks must be dense and equally spaced" % name
+    return ld, t.untyped_storage().nbytes() // 4 - t.storage_offset()
+
+
+def jpeg_dct_inputs(coef, desc_dev, desc_host, tables_dev, tables_host, outs, stream=None):
+    """dj_jpeg_dct_inputs: `coef` the 1-D uint8 CUDA tensor holding the raw int16 coefficient planes, `desc_dev` the
+    descriptors' bytes on the device and `desc_host` the same as a numpy array of data/coefficient_inputs.py:DESC_DTYPE,
+    `tables_dev` the quantisation tables' bytes on the device (1-D uint8) and `tables_host` the same as an int32 numpy
+    array (only its size is read), `outs` = (Y, Cb, Cr): float32 CUDA views of (n, yh, yw, 64) and twice (n, ch, cw, 64)
+    whose blocks may be strided (Cb and Cr may be the halves of one 128-channel tensor).  Every element of the three is
+    written.  `stream`: a HIP stream handle (None: the current launch stream)."""
+    import numpy as np
+    from ._lib import JpegDctDesc
+    from .data.coefficient_inputs import DESC_DTYPE
+    n = _check_staged(desc_host, DESC_DTYPE, JpegDctDesc, desc_dev,
+                      ((coef, "coef"), (desc_dev, "desc_dev"), (tables_dev, "tables_dev")))
+    assert isinstance(tables_host, np.ndarray) and tables_host.dtype == np.int32, "tables_host: expected an int32 array"
+    assert tables_dev.numel() >= tables_host.nbytes, "tables_dev: smaller than the tables"
+    y, cb, cr = outs
+    assert y.dim() == 4 and cb.dim() == 4 and tuple(cb.shape) == tuple(cr.shape), "outs: expected (Y, Cb, Cr) block tensors"
+    (yh, yw), (ch, cw) = y.shape[1:3], cb.shape[1:3]
+    args = []
+    for t, name, rows, cols in ((y, "Y", yh, yw), (cb, "Cb", ch, cw), (cr, "Cr", ch, cw)):
+        ld, floats = _block_stride(t, name, n, rows, cols)
+        args += [ptr(t), ld, floats]
+    check(_L().dj_jpeg_dct_inputs(ptr(coef), coef.numel(), ptr(desc_dev), desc_host.ctypes.data, n, ptr(tables_dev),
+                                  tables_host.size, yh, yw, ch, cw, *args, stream if stream is not None else _stream()),
+          "dj_jpeg_dct_inputs")
+    return outs
+
+
 # ---- Pascal-VOC evaluation: greedy matching, then cumulative counts / precision / recall / sampled AP -------------------------
 def _check_eval_tensor(t, name, dtype, numel):
     assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel, \

@@ -1,2 +1,4 @@
-from .generators import DCTGeneratorJPEG2DCT, DCTGeneratorJPEG2DCTDeconv, device_switches, prepare_imagenet  # noqa: F401
+from .coefficient_generators import DCTGeneratorCoefficients, DCTGeneratorCoefficientsDeconv  # noqa: F401
+from .generators import (DCTGeneratorJPEG2DCT, DCTGeneratorJPEG2DCTDeconv, coefficient_switch, device_switches,  # noqa: F401
+                         prepare_imagenet)
 from .helper import brightness, contrast, grayscale, lighting, saturation  # noqa: F401

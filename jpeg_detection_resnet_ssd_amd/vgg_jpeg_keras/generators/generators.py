@@ -59,6 +59,19 @@ def device_switches(environ=os.environ):
             "decode_threads": int(environ.get("DJ_DECODE_THREADS", "16"))}
 
 
+def coefficient_switch(environ=os.environ):
+    """Whether the configurations feed the DCT architectures the files' own coefficients
+    (coefficient_generators.py): `DJ_COEFFICIENT_INPUTS=1`.  That path has no pixels to prepare or distort, so combining it
+    with `DJ_DEVICE_PREP`, `DJ_DEVICE_DECODE` or `DJ_PHOTOMETRIC` is a ValueError."""
+    if environ.get("DJ_COEFFICIENT_INPUTS", "0") != "1":
+        return False
+    clash = [k for k in ("DJ_DEVICE_PREP", "DJ_DEVICE_DECODE", "DJ_PHOTOMETRIC") if environ.get(k, "0") == "1"]
+    if clash:
+        raise ValueError("DJ_COEFFICIENT_INPUTS=1 cannot be combined with %s: the files' own coefficients are fed to the "
+                         "model, there are no pixels to prepare or distort" % ", ".join(clash))
+    return True
+
+
 class DCTGeneratorJPEG2DCT(Sequence):
     """Batches of `[X_y, X_cbcr]` ((B, T/8, T/8, 64), (B, T/16, T/16, 128)) and one-hot labels."""
     deconv = False

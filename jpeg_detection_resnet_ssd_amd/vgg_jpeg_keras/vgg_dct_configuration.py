@@ -8,7 +8,9 @@ Data: with `DJ_TRAIN_DIR`, `DJ_VAL_DIR` and `DJ_INDEX_FILE` all set, DCTGenerato
 one with `scale=True` and the four photometric transformations when `DJ_PHOTOMETRIC=1`, the validation one with
 `scale=False`; `DJ_DEVICE_PREP=1` moves resize, crop, flip and the JPEG transform to the GPU, and `DJ_DEVICE_DECODE=1` on
 top of it (an error without it) the decoding of baseline JPEG files, read on `DJ_DECODE_THREADS` host threads (default 16).
-Otherwise synthetic
+`DJ_COEFFICIENT_INPUTS=1` (with none of those switches, else an error) feeds pre-sized baseline 4:2:0 files as their own
+coefficients instead (generators/coefficient_generators.py): random window and mirror for training, the centred window for
+validation and test.  Otherwise synthetic
 [Y 28x28x64, CbCr 14x14x128] batches with one-hot labels.  `prepare_testing_generator` reads `DJ_TEST_DIR`, or `DJ_VAL_DIR`
 without it, with `DJ_INDEX_FILE`."""
 from os import environ
@@ -123,20 +125,35 @@ class VGGDCTTrainingConfiguration(object):
         directory = environ.get("DJ_TEST_DIR") or environ.get("DJ_VAL_DIR")
         index_file = environ.get("DJ_INDEX_FILE")
         if directory and index_file:
-            from .generators import DCTGeneratorJPEG2DCT, device_switches
+            from .generators import DCTGeneratorJPEG2DCT, coefficient_switch, device_switches
             self.validation_directory, self.index_file = directory, index_file
-            self._test_generator = DCTGeneratorJPEG2DCT(directory, index_file, self._batch_size, scale=False,
-                                                        **device_switches())
+            if coefficient_switch():
+                self._test_generator = self._coefficient_generator(directory, index_file, training=False)
+            else:
+                self._test_generator = DCTGeneratorJPEG2DCT(directory, index_file, self._batch_size, scale=False,
+                                                            **device_switches())
         else:
             self._test_generator = SyntheticVGGDCTGenerator(self._batch_size, self.num_classes, n_batches=8, seed=999983)
+
+    def _coefficient_generator(self, directory, index_file, training):
+        """`DJ_COEFFICIENT_INPUTS=1`: pre-sized files fed as their own coefficients -- a random window and mirror for
+        training, the centred window and no mirror for validation and test."""
+        from .generators import DCTGeneratorCoefficients
+        return DCTGeneratorCoefficients(directory, index_file, self._batch_size, target_length=self.img_size[0],
+                                        random_crop=training, flip=training,
+                                        decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")))
 
     def prepare_training_generators(self):
         rank = self.horovod.rank() if self.horovod is not None else 0
         real = [environ.get(k) for k in ("DJ_TRAIN_DIR", "DJ_VAL_DIR", "DJ_INDEX_FILE")]
         if all(real):
-            from .generators import DCTGeneratorJPEG2DCT, device_switches
-            switches = device_switches()
+            from .generators import DCTGeneratorJPEG2DCT, coefficient_switch, device_switches
             self.train_directory, self.validation_directory, self.index_file = real
+            if coefficient_switch():
+                self._train_generator = self._coefficient_generator(real[0], real[2], training=True)
+                self._validation_generator = self._coefficient_generator(real[1], real[2], training=False)
+                return
+            switches = device_switches()
             transformations = None
             if environ.get("DJ_PHOTOMETRIC", "0") == "1":
                 from .generators import brightness, contrast, lighting, saturation

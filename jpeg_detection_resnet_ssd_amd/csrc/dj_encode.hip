@@ -75,7 +75,7 @@ __global__ __launch_bounds__(DJ_ENC_THREADS) void dj_ssd_encode_kernel(DjEncodeP
   __shared__ int n_redo;
   __shared__ int match[DJ_ENC_GT_CAP];
   __shared__ unsigned char gt_done[DJ_ENC_GT_CAP];
-  __shared__ short assign[DJ_ENC_BOX_CAP];  // -1 unmatched, -2 neutral, -3 taken by the bipartite pass (temporary), >= 0 gt
+  __shared__ short assign[DJ_ENC_BOX_CAP];  // -1 unmatched, -2 neutral, -3 column zeroed (greedy loop only), >= 0 gt
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = DJ_ENC_THREADS / 64;
   const int n = min(p.n_gt[img], p.max_gt);
   const double d = (double)p.border;
@@ -183,6 +183,13 @@ __global__ __launch_bounds__(DJ_ENC_THREADS) void dj_ssd_encode_kernel(DjEncodeP
       }
       __syncthreads();
     }
+    // The -3 marks stand for the columns zeroed in the loop's copy of the matrix only.  Afterwards the reference clears
+    // the columns of the FINAL matches (sim[:, bipartite_matches] = 0): a round in which every remaining overlap is 0
+    // re-picks ground truth 0 and moves its match to anchor 0, and the anchor it held before is an ordinary column again
+    // for the multi / neutral step below.
+    for (int a = tid; a < N; a += DJ_ENC_THREADS)
+      if (assign[a] == -3) assign[a] = -1;
+    __syncthreads();
     // y_encoded[i, bipartite_matches, :-8] = labels_one_hot  (duplicate indices: the last ground truth wins)
     if (tid == 0)
       for (int g = 0; g < n; ++g) assign[match[g]] = (short)g;

@@ -107,6 +107,37 @@ def decode_fixture():
     print("decode fixture: kept", [d.shape for d in dec], [d.shape for d in dec2], [d.shape for d in fast])
 
 
+def small_options_fixture():
+    """The reference's SSDInputEncoder on the small 68-anchor family of tests/encode_cases.py: per option set the quirk, tie
+    and border-mode cases in one batch, the two exact-threshold cases and the twin-anchor case.  Each entry holds the ground
+    truth flat plus counts, the option values (JSON) and the reference's y_true."""
+    import json
+    sys.path.insert(0, os.path.dirname(OUT))
+    import encode_cases as ec
+    entries = {}
+
+    def add(key, kwargs, images):
+        y = SSDInputEncoder(**kwargs)(images)
+        assert np.isfinite(y).all(), key
+        entries[key + ".options"] = np.array(json.dumps(kwargs))
+        entries[key + ".gt_count"] = np.array([len(g) for g in images])
+        entries[key + ".gt"] = np.concatenate([g for g in images if len(g)])
+        entries[key + ".y_true"] = y.astype(np.float64)
+
+    for opt, over in ec.OPTION_SETS.items():
+        images, _ = ec.batch(ec.small_encoder(**over), names=ec.GOLDEN_CASES)
+        add(opt + ".cases", ec.small_kwargs(**over), images)
+        for which in ("pos", "neg"):
+            _, images, _, kw = ec.threshold_case(which, **over)
+            add(opt + ".threshold_" + which, ec.small_kwargs(**kw), images)
+        _, images, _ = ec.twin_case(**over)
+        add(opt + ".twin", ec.small_kwargs(**dict(over, **ec.TWIN)), images)
+    path = os.path.join(OUT, "encoder_small_options.npz")
+    np.savez_compressed(path, **entries)
+    print("small options fixture:", len(entries) // 4, "entries,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     main()
     decode_fixture()
+    small_options_fixture()

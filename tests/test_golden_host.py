@@ -107,6 +107,32 @@ def test_encoder_other_coordinate_modes():
         SSDInputEncoder(300, 300, 3, [(4, 4)], variances=[0.1, 0.1, 0.2])
 
 
+def test_encoder_small_family_options_match_reference():
+    """Every option axis of the encoder (border pixels, pixel / normalised coordinates, clipping, background id, matching
+    type, thresholds hit exactly, variances, steps / offsets) on the greedy-matching quirk, tie and border cases of
+    tests/encode_cases.py: the host encoder reproduces what the reference's own encoder wrote, exactly."""
+    import json
+    from jpeg_detection_resnet_ssd_amd.ssd_encoder_decoder.ssd_input_encoder import SSDInputEncoder
+    import encode_cases as ec
+    f = load("encoder_small_options.npz")
+    keys = sorted(k[:-len(".y_true")] for k in f if k.endswith(".y_true"))
+    assert keys == sorted("%s.%s" % (o, e) for o in ec.OPTION_SETS
+                          for e in ("cases", "threshold_pos", "threshold_neg", "twin"))
+    seen = set()
+    for key in keys:
+        kwargs = json.loads(str(f[key + ".options"]))
+        gt = split_gt({"gt": f[key + ".gt"], "gt_count": f[key + ".gt_count"]})
+        y = SSDInputEncoder(**kwargs)(gt)
+        assert y.shape == f[key + ".y_true"].shape and np.isfinite(y).all()
+        np.testing.assert_array_equal(y, f[key + ".y_true"], err_msg=key)
+        seen.add((kwargs["border_pixels"], kwargs["matching_type"]))
+        opt, entry = key.rsplit(".", 1)
+        if entry == "cases":            # the stored ground truth is what the cases build today
+            now, _ = ec.batch(ec.small_encoder(**ec.OPTION_SETS[opt]), names=ec.GOLDEN_CASES)
+            assert len(now) == len(gt) and all(np.array_equal(a, b) for a, b in zip(now, gt))
+    assert {b for b, _ in seen} == {"half", "include", "exclude"} and {m for _, m in seen} == {"multi", "bipartite"}
+
+
 def test_anchor_layer_agrees_with_encoder_template():
     """AnchorBoxes (model side) and SSDInputEncoder (target side) must produce the same anchors in the same order
     -- the contract between y_pred and y_true rows (keras_ssd300_dct_j2d_resnet.py:775-879 vs ssd_input_encoder.py:574-591)."""

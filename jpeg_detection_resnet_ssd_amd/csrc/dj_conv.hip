@@ -402,6 +402,13 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
   }
   p.b_bytes = extent_bytes((long)p.K, d->out_c, d->out_c, dt_size(a.dt_w));
   p.b_dt = a.dt_w;
+  // (refusals come before the first write: a split launch clears y below)
+  if (a.res) {
+    DJ_CHECK_ARG(dj_fast_mode_fwd(p) == 3, "conv fwd (residual add): the branch-free kernel's preconditions do not hold "
+                                           "(channels %% 32, 16-byte aligned tensors)");
+  }
+  DJ_CHECK_ARG(!io16 || dj_fast_mode_fwd(p) != 0, "conv fwd: 16-bit tensors need the branch-free kernel's preconditions "
+                                                  "(in_c %% 32 == 0, out_c %% 4 == 0, 16-byte aligned tensors)");
   // statistics come out of the GEMM epilogue (one K range per tile) -- or, for a caller that allows it and supplies a
   // workspace, out of the slab reduction of a split launch (tuned like a launch without statistics)
   const bool wants_stats = a.stats != nullptr && !stats_may_split;
@@ -428,12 +435,6 @@ extern "C" int dj_conv2d_nhwc_fwd(const dj_conv2d_desc* d, const dj_conv_fwd_arg
     if (!y_zeroed)
       if (int rc = clear_rows(y, p.M, d->out_c, d->ld_y, 4, s, "conv fwd")) return rc;
   }
-  if (a.res) {
-    DJ_CHECK_ARG(dj_fast_mode_fwd(p) == 3, "conv fwd (residual add): the branch-free kernel's preconditions do not hold "
-                                           "(channels %% 32, 16-byte aligned tensors)");
-  }
-  DJ_CHECK_ARG(!io16 || dj_fast_mode_fwd(p) != 0, "conv fwd: 16-bit tensors need the branch-free kernel's preconditions "
-                                                  "(in_c %% 32 == 0, out_c %% 4 == 0, 16-byte aligned tensors)");
   if (int rc = dj_launch_cfg<0, 0>(cfg, p, splits, s)) return rc;
   if (slabs) return launch_splitk_reduce(ws, splits, p.slab_stride, p.M, p.N, a.bias, relu, y, d->ld_y, a.stats, s);
   if (splits > 1 && relu) {
@@ -553,13 +554,14 @@ extern "C" int dj_conv2d_nhwc_dgrad(const dj_conv2d_desc* d, const dj_conv_dgrad
     p.cH = d->in_h;
     p.cW = d->in_w;
     p.cS = d->stride_h;
+    // (refused before dx is cleared)
+    DJ_CHECK_ARG(!io16 || (fast_mode<0, 1>(p)) != 0, "conv dgrad (strided 1x1): 16-bit tensors need the branch-free kernel's "
+                                                   "preconditions (channels %% 32, 16-byte aligned tensors)");
     if (!beta)
       if (int rc = clear_rows(a.dx, in_pixels, d->in_c, d->ld_x, dt_size(a.dt_dx), s, "conv dgrad")) return rc;
     int cfg = choose_cfg(p.M, p.N, p.K, false, &splits);
     tune_lookup(1, d, &cfg, &splits);
     split_k(p.K, 1, &p.kchunk);
-    DJ_CHECK_ARG(!io16 || (fast_mode<0, 1>(p)) != 0, "conv dgrad (strided 1x1): 16-bit tensors need the branch-free kernel's "
-                                                   "preconditions (channels %% 32, 16-byte aligned tensors)");
     return dj_launch_cfg<0, 1>(cfg, p, 1, s);
   }
   p.M = (int)in_pixels;
@@ -662,6 +664,8 @@ extern "C" int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const dj_conv_wgrad
   p.b_bytes = extent_bytes((long)d->batch * d->out_h * d->out_w, d->ld_y, d->out_c, dt_size(a.dt_dy));
   p.a_dt = a.dt_x;
   p.b_dt = a.dt_dy;
+  DJ_CHECK_ARG(!io16 || (fast_mode<2, 0>(p)) != 0, "conv wgrad: 16-bit tensors need the branch-free kernel's preconditions "
+                                                 "(channels %% 4, 16-byte aligned tensors)");
   int splits = 1;
   int cfg = choose_cfg_wgrad(p.M, p.N, p.K, &splits);
   tune_lookup(2, d, &cfg, &splits);
@@ -671,8 +675,6 @@ extern "C" int dj_conv2d_nhwc_wgrad(const dj_conv2d_desc* d, const dj_conv_wgrad
     if (!a.dw_zeroed)
       if (int rc = memset_status(hipMemsetAsync(a.dw, 0, (size_t)p.M * p.N * 4, s), "conv wgrad")) return rc;
   }
-  DJ_CHECK_ARG(!io16 || (fast_mode<2, 0>(p)) != 0, "conv wgrad: 16-bit tensors need the branch-free kernel's preconditions "
-                                                 "(channels %% 4, 16-byte aligned tensors)");
   return dj_launch_cfg<2, 0>(cfg, p, splits, s);
 }
 

@@ -34,7 +34,7 @@ from jpeg_detection_resnet_ssd_amd.keras.metrics import top_k_categorical_accura
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
 from jpeg_detection_resnet_ssd_amd.keras.utils import Sequence
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.evaluation import Evaluator
-from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import coefficient_switch, device_switches
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import coefficient_switch, device_entropy_switch, device_switches
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 
 
@@ -185,7 +185,8 @@ class TrainingConfiguration(object):
                                                                              DCTGeneratorCoefficientsDeconv)
         cls = DCTGeneratorCoefficientsDeconv if self.deconv else DCTGeneratorCoefficients
         return cls(directory, index_file, self._batch_size, target_length=self.img_size[0], random_crop=training,
-                   flip=training, decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")))
+                   flip=training, decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")),
+                   device_entropy=device_entropy_switch())
 
     def _rgb_generator(self, directory, training):
         """The reference's two calls for the RGB ResNet50 (classification_part/config/resnetRGB/config_file.py:157-172)."""

@@ -648,6 +648,47 @@ int dj_jpeg_dct_inputs(const unsigned char* coef, long coef_bytes, const dj_jpeg
                        int cw, float* out_y, long ld_y, long y_floats, float* out_cb, long ld_cb, long cb_floats,
                        float* out_cr, long ld_cr, long cr_floats, void* stream);
 
+/* ---- Huffman entropy decoding of restart-interval JPEG files, one lane per restart interval ("segment"), to the RAW int16
+ * planes dj_jpeg_read_raw_batch would have written -- bit for bit what data/entropy_decode.py:entropy_decode_host states
+ * (its docstring holds the rules: the bit source with FF 00 unstuffing, the DC and AC rules of the host reader's
+ * decode_block, the statuses 1..4, "a failing block and every later block of its segment are zero").  The host half is
+ * dj_jpeg_scan_segments (include/dj_jpeg_segments.h), which finds the segments and builds the tables.
+ * bytes: the files' bytes, anywhere inside `n_bytes`; segment record s = bytes [begin, end), the file it belongs to and
+ * the MCUs it holds ([first_mcu, first_mcu + n_mcus) of that file, in scan order).  File descriptor i: component c's plane
+ * is blocks_h[c] x blocks_w[c] x 64 values in natural order at out + plane_offset[c] (bytes, a multiple of 16; out itself
+ * 16-byte aligned), of which plane_capacity[c] values are the caller's; h_blocks / v_blocks are its blocks per MCU,
+ * dc_table / ac_table index the file's tables (0..3), which start at table `table_first` of `tables` (n_tables tables of
+ * DJ_JPEG_HUFF_BYTES = 896 bytes in the device form of dj_jpeg_segments.h, `tables` 16-byte aligned); its segments are
+ * records [seg_first, seg_first + n_segments) and must tile its mcus_x * mcus_y MCUs in order.
+ * EVERY element of every plane is written (zeros included), and status[s] = 0 or 1..4 for every segment.
+ * bytes / desc_dev / seg_dev / tables / out / status are DEVICE pointers; desc_host and seg_host the HOST copies of the
+ * descriptors and records, read during the call only: every byte range, plane offset and capacity, table index, block
+ * and MCU count is checked against the sizes given before anything is launched, and an error launches nothing and writes
+ * nothing.  The kernel clips every read to [0, n_bytes) and every store to the plane's capacity and out_bytes again, from
+ * what it reads on the device, so device data that differs from the host copies gives wrong values and a status, never
+ * an access outside the buffers given.  One launch, no synchronisation: capturable. ---- */
+typedef struct dj_jpeg_entropy_desc {
+  long plane_offset[3];            /* bytes */
+  long plane_capacity[3];          /* int16 values */
+  int blocks_h[3], blocks_w[3];
+  int h_blocks[3], v_blocks[3];    /* blocks per MCU across / down */
+  int dc_table[3], ac_table[3];    /* 0..3 */
+  int table_first;                 /* tables */
+  int n_components;                /* 1 or 3 */
+  int mcus_x, mcus_y;
+  int seg_first, n_segments;
+} dj_jpeg_entropy_desc;
+typedef struct dj_jpeg_entropy_seg {
+  long begin, end;                 /* bytes */
+  int file;
+  int first_mcu, n_mcus;
+  int reserved;
+} dj_jpeg_entropy_seg;
+int dj_jpeg_entropy_decode(const unsigned char* bytes, long n_bytes, const dj_jpeg_entropy_desc* desc_dev,
+                           const dj_jpeg_entropy_desc* desc_host, int n_files, const dj_jpeg_entropy_seg* seg_dev,
+                           const dj_jpeg_entropy_seg* seg_host, int n_segments, const unsigned char* tables, int n_tables,
+                           unsigned char* out, long out_bytes, int* status, void* stream);
+
 /* ---- Pascal-VOC evaluation (L/eval_utils/average_precision_evaluator.py:570-925): `Evaluator.match_predictions`,
  * `compute_precision_recall` and `compute_average_precisions(mode='sample')` with results equal bit for bit to the host
  * methods (float64, their operation order; eval_utils/device_matching.py packs the inputs and restates the segment-wise

@@ -46,4 +46,8 @@ int dj_jpeg_read_raw_batch(const unsigned char* const* data, const long* sizes, 
 #ifdef __cplusplus
 }
 #endif
+
+/* the pre-pass of entropy decoding on the GPU, kept in a header of its own */
+#include "dj_jpeg_segments.h"
+
 #endif

@@ -63,7 +63,7 @@ def build_library(force=False, verbose=False):
 def build_jpeg_library(force=False):
     """Host-only JPEG coefficient reader (csrc/dj_jpeg.cpp -> csrc/libdj_jpeg.so), plain g++."""
     src = os.path.join(CSRC, "dj_jpeg.cpp")
-    hdrs = [os.path.join(CSRC, "..", "..", "include", h) for h in ("dj_jpeg.h", "dj_jpeg_decode.h")]
+    hdrs = [os.path.join(CSRC, "..", "..", "include", h) for h in ("dj_jpeg.h", "dj_jpeg_decode.h", "dj_jpeg_segments.h")]
     if force or _newer([src] + hdrs, JPEG_LIB_PATH):
         cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", src, "-o",
                JPEG_LIB_PATH]

@@ -47,6 +47,16 @@ class JpegDctDesc(Structure):   # dj_jpeg_dct_desc
                 + [(n, c_int) for n in ("table_offset", "n_components", "flip")])
 
 
+class JpegEntropyDesc(Structure):   # dj_jpeg_entropy_desc
+    _fields_ = ([("plane_offset", c_long * 3), ("plane_capacity", c_long * 3)]
+                + [(n, c_int * 3) for n in ("blocks_h", "blocks_w", "h_blocks", "v_blocks", "dc_table", "ac_table")]
+                + [(n, c_int) for n in ("table_first", "n_components", "mcus_x", "mcus_y", "seg_first", "n_segments")])
+
+
+class JpegEntropySeg(Structure):   # dj_jpeg_entropy_seg
+    _fields_ = [("begin", c_long), ("end", c_long), ("file", c_int), ("first_mcu", c_int), ("n_mcus", c_int), ("reserved", c_int)]
+
+
 class PhotometricOps(Structure):   # dj_photometric_ops
     _fields_ = [("n_ops", c_int), ("code", c_int * 4), ("reserved", c_int), ("param", (c_double * 3) * 4)]
 
@@ -208,6 +218,8 @@ SIGNATURES = {
                                c_long, c_void_p]),
     "dj_jpeg_dct_inputs": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_int, c_int,
                                    FP, c_long, c_long, FP, c_long, c_long, FP, c_long, c_long, c_void_p]),
+    "dj_jpeg_entropy_decode": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_long, c_void_p, c_void_p]),
     "dj_eval_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
                               c_void_p]),

@@ -38,11 +38,13 @@ struct Huff {
   int32_t mincode[17];
   int valptr[17];
   unsigned char vals[256];
+  unsigned char counts[16];  // codes per length, as the DHT segment gave them
   // one-step table on the next 9 bits: (length << 8) | symbol, 0 = longer code
   uint16_t fast[512];
 
   int build(const unsigned char counts[16], const unsigned char* symbols, int n) {
     memcpy(vals, symbols, (size_t)n);
+    memcpy(this->counts, counts, 16);
     memset(fast, 0, sizeof(fast));
     int code = 0, k = 0;
     for (int l = 1; l <= 16; ++l) {
@@ -174,6 +176,10 @@ struct Decoder {
   bool strict = false;   // a scan that ends before its last MCU, or a file without EOI, is an error (no zero-filled tail)
   bool saw_eoi = false;
   Scratch* scratch = nullptr;
+  // where a headers-only run stopped: the first scan's header and the first byte of its entropy-coded data
+  const unsigned char* sos_body = nullptr;
+  int sos_len = 0;
+  const unsigned char* ecs = nullptr;
 
   static int be16(const unsigned char* p) { return (p[0] << 8) | p[1]; }
 
@@ -403,7 +409,12 @@ struct Decoder {
         if (blen < 2) return fail("bad DRI");
         restart_interval = be16(body);
       } else if (m == 0xDA) {
-        if (headers_only) return 0;
+        if (headers_only) {
+          sos_body = body;
+          sos_len = blen;
+          ecs = p + len;
+          return 0;
+        }
         const unsigned char* next = nullptr;
         if (decode_scan(body, blen, p + len, end, &next)) return -1;
         any_scan = true;
@@ -620,6 +631,117 @@ extern "C" int dj_jpeg_read_decode_info(const unsigned char* data, long size, dj
   info->adobe_transform = d.adobe_transform;
   info->precision = d.precision;
   info->device_decodable = device_decodable(d);
+  return 0;
+}
+
+namespace {
+
+// The device form of a table (include/dj_jpeg_segments.h), from what Huff::build kept of the DHT segment
+void device_table(const Huff& h, unsigned char* out) {
+  uint16_t lut[256];
+  int32_t limit[16], offset[16];
+  memset(lut, 0, sizeof(lut));
+  int code = 0, k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    offset[l - 1] = k - code;
+    for (int i = 0; i < h.counts[l - 1]; ++i, ++k, ++code)
+      if (l <= 8)
+        for (int f = code << (8 - l); f < ((code + 1) << (8 - l)); ++f) lut[f] = (uint16_t)((l << 8) | h.vals[k]);
+    limit[l - 1] = code << (16 - l);
+    code <<= 1;
+  }
+  memcpy(out, lut, 512);
+  memcpy(out + 512, limit, 64);
+  memcpy(out + 576, offset, 64);
+  memcpy(out + 640, h.vals, 256);
+}
+
+int not_eligible(dj_jpeg_segment_info* info, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(info->reason, sizeof(info->reason), fmt, ap);
+  va_end(ap);
+  info->entropy_decodable = 0;
+  info->n_segments = 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
+                                     long range_capacity) {
+  if (!data || !info || size <= 0 || (range_capacity > 0 && !ranges)) return fail("scan_segments: null argument");
+  memset(info, 0, sizeof(*info));
+  Decoder d;
+  d.data = data;
+  d.size = size;
+  d.scratch = &g_scratch;
+  if (d.run(true)) return not_eligible(info, "%s", g_err);
+  if (!d.saw_sof) return not_eligible(info, "no frame header before the scan");
+  d.fill_info(&info->decode.base);
+  for (int c = 0; c < d.ncomp; ++c) info->decode.component_id[c] = d.comp[c].id;
+  info->decode.saw_jfif = d.saw_jfif;
+  info->decode.saw_adobe = d.saw_adobe;
+  info->decode.adobe_transform = d.adobe_transform;
+  info->decode.precision = d.precision;
+  info->decode.device_decodable = device_decodable(d);
+  if (!info->decode.device_decodable) return not_eligible(info, "not a file the GPU paths cover (SOF%d, %d components)", d.sof, d.ncomp);
+  if (!d.sos_body) return not_eligible(info, "no scan");
+  const unsigned char* end = data + size;
+  const unsigned char* hdr = d.sos_body;
+  const int ns = d.sos_len >= 1 ? hdr[0] : 0;
+  if (ns != d.ncomp || d.sos_len < 1 + 2 * ns + 3) return not_eligible(info, "the first scan names %d of %d components", ns, d.ncomp);
+  int n_tables = 0, slot_of[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+  for (int i = 0; i < ns; ++i) {
+    if (hdr[1 + 2 * i] != d.comp[i].id) return not_eligible(info, "the scan's components are not in frame order");
+    const int sel[2] = {hdr[2 + 2 * i] >> 4, hdr[2 + 2 * i] & 15};
+    for (int tc = 0; tc < 2; ++tc) {
+      if (sel[tc] > 3 || !(tc ? d.ac : d.dc)[sel[tc]].present) return not_eligible(info, "the scan uses an undefined Huffman table");
+      if (slot_of[tc][sel[tc]] < 0) {
+        if (n_tables == 4) return not_eligible(info, "the scan uses more than four Huffman tables");
+        device_table((tc ? d.ac : d.dc)[sel[tc]], info->tables[n_tables]);
+        slot_of[tc][sel[tc]] = n_tables++;
+      }
+      (tc ? info->ac_table : info->dc_table)[i] = slot_of[tc][sel[tc]];
+    }
+    info->h_blocks[i] = ns == 1 ? 1 : d.comp[i].h;
+    info->v_blocks[i] = ns == 1 ? 1 : d.comp[i].v;
+  }
+  info->n_tables = n_tables;
+  const unsigned char* tail = hdr + 1 + 2 * ns;
+  if (tail[0] != 0 || tail[1] != 63 || tail[2] != 0) return not_eligible(info, "not a sequential scan");
+  if (d.restart_interval <= 0) return not_eligible(info, "no restart interval (DRI)");
+  info->restart_interval = d.restart_interval;
+  info->mcus_x = ns == 1 ? d.comp[0].blocks_w : (d.width + 8 * d.hmax - 1) / (8 * d.hmax);
+  info->mcus_y = ns == 1 ? d.comp[0].blocks_h : (d.height + 8 * d.vmax - 1) / (8 * d.vmax);
+  const long n_mcus = (long)info->mcus_x * info->mcus_y;
+  const long n_segments = (n_mcus + d.restart_interval - 1) / d.restart_interval;
+  // one linear search for 0xFF from the scan's first byte to EOI
+  const bool keep = range_capacity >= n_segments;
+  long seen = 0;
+  const unsigned char* begin = d.ecs;
+  const unsigned char* q = d.ecs;
+  for (;;) {
+    q = q < end ? (const unsigned char*)memchr(q, 0xFF, (size_t)(end - q)) : nullptr;
+    if (!q || q + 1 >= end) return not_eligible(info, "the entropy-coded data ends without an end-of-image marker");
+    const int m = q[1];
+    if (m == 0x00) {
+      q += 2;
+      continue;
+    }
+    if (m == 0xD9) break;
+    if (m < 0xD0 || m > 0xD7) return not_eligible(info, "FF %02X inside or after the entropy-coded data", m);
+    if (m != 0xD0 + (int)(seen & 7)) return not_eligible(info, "restart marker RST%d where RST%d belongs", m - 0xD0, (int)(seen & 7));
+    if (seen + 1 >= n_segments) return not_eligible(info, "more restart markers than the %ld intervals need", n_segments);
+    if (keep) ranges[2 * seen] = begin - data, ranges[2 * seen + 1] = q - data;
+    ++seen;
+    q += 2;
+    begin = q;
+  }
+  if (seen + 1 != n_segments) return not_eligible(info, "%ld restart markers where %ld belong", seen, n_segments - 1);
+  if (keep) ranges[2 * seen] = begin - data, ranges[2 * seen + 1] = q - data;
+  info->n_segments = (int)n_segments;
+  info->entropy_decodable = 1;
   return 0;
 }
 

@@ -24,6 +24,12 @@ axis).  Output block column j of a component takes window block column n_cols - 
 coefficient of odd v (k & 1) is negated: cos((2(7 - x) + 1) v pi / 16) = (-1)^v cos((2x + 1) v pi / 16).  The negation is
 applied to the int16 value, with int16's wrap-around (-(-32768) = -32768), before the conversion to float.
 
+Entropy decoding on the GPU (opt-in, `DeviceCoefficientInputs(device_entropy=True)`): a batch whose files all carry restart
+intervals (jpeg2dct/numpy.py:`scan_segments` decides) uploads the files' bytes instead of their planes, and
+csrc/dj_jpeg_entropy.hip (`kernels.jpeg_entropy_decode`) makes the same raw planes in device scratch, one restart interval
+per lane, as data/entropy_decode.py states; any other batch takes the host reader whole.  The numbers that reach the model
+are the same bit for bit.
+
 All arithmetic here is int32 / int16."""
 import numpy as np
 
@@ -213,21 +219,157 @@ class CoefficientPlan(ds.StagedPlan):
         return out
 
 
+# dj_jpeg_entropy_desc and dj_jpeg_entropy_seg (include/dj_hip.h), C layout
+ENTROPY_DTYPE = np.dtype([("plane_offset", np.int64, 3), ("plane_capacity", np.int64, 3)]
+                         + [(n, np.int32, 3) for n in ("blocks_h", "blocks_w", "h_blocks", "v_blocks", "dc_table", "ac_table")]
+                         + [(n, np.int32) for n in ("table_first", "n_components", "mcus_x", "mcus_y", "seg_first",
+                                                    "n_segments")], align=True)
+SEGMENT_DTYPE = np.dtype([("begin", np.int64), ("end", np.int64), ("file", np.int32), ("first_mcu", np.int32),
+                          ("n_mcus", np.int32), ("reserved", np.int32)], align=True)
+
+
+def segment_scan(image):
+    """The pre-pass's verdict and findings for a `CoefficientImage` (jpeg2dct/numpy.py:`scan_segments`), made once per
+    file where its header is parsed and kept on the image."""
+    scan = getattr(image, "_segment_scan", None)
+    if scan is None:
+        bh, bw = image.grids()[0]
+        scan = image._segment_scan = reader.scan_segments(image.data, max_segments=bh * bw)
+    return scan
+
+
+def entropy_records(scans, plane_offsets, file_offsets):
+    """-> (ENTROPY_DTYPE descriptors, SEGMENT_DTYPE records, (n_tables, HUFF_BYTES) uint8 tables) of a batch of eligible
+    files: plane_offsets[i][c] the byte offset of file i's plane c in the output buffer, file_offsets[i] that of its
+    first byte in the bytes buffer.  File i's tables are the four from 4 i on (unused ones zero)."""
+    n = len(scans)
+    desc = np.zeros(n, dtype=ENTROPY_DTYPE)
+    counts = np.array([s.n_segments for s in scans], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    mcus = np.array([s.mcus for s in scans], dtype=np.int64)
+    interval = np.array([s.restart_interval for s in scans], dtype=np.int64)
+    desc["table_first"], desc["n_components"] = 4 * np.arange(n), [s.n_components for s in scans]
+    desc["mcus_y"], desc["mcus_x"], desc["seg_first"], desc["n_segments"] = mcus[:, 0], mcus[:, 1], first, counts
+
+    def per_component(values, absent=0):      # [[per component] per file] -> (n, 3), absent components 0
+        return [tuple(v) + (absent,) * (3 - len(v)) for v in values]
+    grids = np.array(per_component([s.grids for s in scans], (0, 0)), dtype=np.int64)            # (n, 3, 2)
+    blocks = np.array(per_component([s.mcu_blocks for s in scans], (0, 0)), dtype=np.int64)
+    desc["blocks_h"], desc["blocks_w"], desc["v_blocks"], desc["h_blocks"] = grids[..., 0], grids[..., 1], blocks[..., 0], blocks[..., 1]
+    desc["dc_table"], desc["ac_table"] = per_component([s.dc_table for s in scans]), per_component([s.ac_table for s in scans])
+    desc["plane_offset"] = np.asarray([tuple(o)[:3] for o in plane_offsets], dtype=np.int64) * (grids[..., 0] > 0)
+    desc["plane_capacity"] = grids[..., 0] * grids[..., 1] * 64
+    tables = np.concatenate([s.tables4 for s in scans])
+    segs = np.zeros(int(counts.sum()), dtype=SEGMENT_DTYPE)
+    ranges = np.concatenate([s.ranges for s in scans]) + np.repeat(np.asarray(file_offsets[:n], dtype=np.int64), counts)[:, None]
+    segs["begin"], segs["end"], segs["file"] = ranges[:, 0], ranges[:, 1], np.repeat(np.arange(n), counts)
+    segs["first_mcu"] = (np.arange(len(segs)) - np.repeat(first, counts)) * np.repeat(interval, counts)
+    segs["n_mcus"] = np.minimum(np.repeat(interval, counts), np.repeat(mcus[:, 0] * mcus[:, 1], counts) - segs["first_mcu"])
+    return desc, segs, tables
+
+
+class EntropyCoefficientPlan(CoefficientPlan):
+    """The plan of a batch whose files are all entropy-decodable on the GPU (restart intervals; `segment_scan`): one staging
+    blob `[dj_jpeg_dct descriptors | quantisation tables | entropy descriptors | segment records | Huffman tables | file
+    bytes]`, every part at a multiple of 64 bytes.  The raw coefficient planes are not uploaded: they live in the
+    per-device scratch (`scratch_bytes`: every plane at a multiple of 64 bytes, then one int32 status per segment), where
+    dj_jpeg_entropy_decode writes them from the files' bytes and dj_jpeg_dct_inputs reads them.  `fill` copies bytes and
+    starts no thread."""
+
+    def __init__(self, images, windows, flips, grids, scans):
+        CoefficientPlan.__init__(self, images, windows, flips, grids)      # descriptors, tables, plane offsets
+        self.file_offsets = np.concatenate([[0], np.cumsum([len(im.data) for im in images])]).astype(np.int64)
+        self.entropy, self.segments, self.huffman = entropy_records(scans, self.plane_offsets, self.file_offsets)
+        self.n_status = len(self.segments)
+        self.status_offset = self.coef_bytes                               # in the scratch, behind the planes
+        self.scratch_bytes = self.coef_bytes + 4 * self.n_status
+        self._lay_out([("desc", self.desc), ("tables", self.tables), ("entropy", self.entropy), ("segments", self.segments),
+                       ("huffman", self.huffman), ("bytes", int(self.file_offsets[-1]))])
+
+    def fill(self, staging, images, n_threads=None):
+        """Write descriptors, records, tables and the files' bytes into `staging`, a uint8 numpy array of at least
+        `nbytes`.  Nothing is decoded here."""
+        for offset, content in self.parts:
+            staging[offset:offset + content.size] = content
+        for im, at in zip(images, self.file_offsets + self.bytes_offset):
+            staging[at:at + len(im.data)] = np.frombuffer(im.data, dtype=np.uint8)
+
+    def entropy_views(self, blob):
+        """(entropy descriptors, segment records, Huffman tables, file bytes) of a staging buffer or of its device copy."""
+        desc = self.part(blob, self.entropy_offset, self.entropy, ENTROPY_DTYPE)
+        segs = self.part(blob, self.segments_offset, self.segments, SEGMENT_DTYPE)
+        huff = self.part(blob, self.huffman_offset, self.huffman)
+        if isinstance(blob, np.ndarray):
+            huff = huff.reshape(self.huffman.shape)
+        return desc, segs, huff, blob[self.bytes_offset:self.bytes_offset + int(self.file_offsets[-1])]
+
+    def views(self, blob):
+        """(descriptors, tables) of dj_jpeg_dct_inputs in a staging buffer or its device copy; the planes are in the scratch."""
+        return (self.part(blob, self.desc_offset, self.desc, DESC_DTYPE), self.part(blob, self.tables_offset, self.tables, np.int32),
+                None)
+
+    def status_view(self, scratch):
+        """The int32 statuses, one per segment, where `launch` had them written in `scratch`."""
+        import torch
+        return scratch[self.status_offset:self.status_offset + 4 * self.n_status].view(torch.int32)
+
+    def launch(self, blob_host, blob_dev, out, scratch=None, stream=None):
+        """dj_jpeg_entropy_decode into `scratch` (a 1-D uint8 CUDA tensor of at least `scratch_bytes`, 16-byte aligned),
+        then dj_jpeg_dct_inputs from it into `out`."""
+        from .. import kernels
+        if scratch is None or scratch.numel() < self.scratch_bytes:
+            raise ValueError("this plan needs %d bytes of device scratch" % self.scratch_bytes)
+        desc_h, tables_h, _ = self.views(blob_host)
+        desc_d, tables_d, _ = self.views(blob_dev)
+        edesc_h, segs_h, huff_h, _ = self.entropy_views(blob_host)
+        edesc_d, segs_d, huff_d, bytes_d = self.entropy_views(blob_dev)
+        planes = scratch[:self.coef_bytes]
+        kernels.jpeg_entropy_decode(bytes_d, edesc_d, edesc_h, segs_d, segs_h, huff_d, huff_h, planes, self.status_view(scratch),
+                                    stream=stream)
+        outs = tuple(out) if len(out) == 3 else (out[0], out[1][..., :64], out[1][..., 64:])
+        kernels.jpeg_dct_inputs(planes, desc_d, desc_h, tables_d, tables_h, outs, stream=stream)
+        return out
+
+    def failures(self, status, images):
+        """The text naming the files whose segments failed, from the plan's downloaded statuses; None when all are 0."""
+        from .entropy_decode import STATUS_TEXT
+        status = np.asarray(status)[:self.n_status]
+        if not status.any():
+            return None
+        bad = []
+        for i, d in enumerate(self.entropy):
+            mine = status[d["seg_first"]:d["seg_first"] + d["n_segments"]]
+            if mine.any():
+                k = int(np.flatnonzero(mine)[0])
+                bad.append("file %d%s: segment %d: %s" % (i, " (%s)" % images[i].name if getattr(images[i], "name", None) else "",
+                                                          k, STATUS_TEXT.get(int(mine[k]), "status %d" % mine[k])))
+        return "entropy decoding on the GPU failed for " + "; ".join(bad)
+
+
 class PendingCoefficientInputs(PendingInputs):
     """The files of one batch with their windows and mirrors, on their way into a model's resident input buffers
     (`Model.train_on_batch / predict / fit_generator` accept it where they accept the list of input arrays): at upload time
     the files' raw planes are entropy-decoded into pinned memory, one copy takes `[descriptors | tables | planes]` up
-    and one launch of dj_jpeg_dct_inputs writes the inputs.  `shape` is that of the pixel batch the windows stand for."""
+    and one launch of dj_jpeg_dct_inputs writes the inputs.  `shape` is that of the pixel batch the windows stand for.
+    With an emitter whose `device_entropy` is set and a batch whose files are ALL entropy-decodable on the GPU, the files'
+    bytes go up instead and dj_jpeg_entropy_decode makes the planes there (`EntropyCoefficientPlan`); a batch with any
+    other file takes the host path whole, and the emitter's `host_batches` counts it."""
 
-    def __init__(self, emitter, files, windows=None, flips=None):
+    def __init__(self, emitter, files, windows=None, flips=None, _count=True):
         self.images = check_files(files)
         self.windows, self.flips, (h, w) = check_batch(self.images, windows, flips)
         # descriptors and layout are made where the batch is made (a generator's prefetch thread), not at upload time
-        self.plan = CoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w))
+        scans = [segment_scan(im) for im in self.images] if getattr(emitter, "device_entropy", False) else None
+        if scans is not None and all(s.entropy_decodable for s in scans):
+            self.plan = EntropyCoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w), scans)
+        else:
+            self.plan = CoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w))
+            if scans is not None and _count:
+                emitter.host_batches += 1
         PendingInputs.__init__(self, emitter, (len(self.images), h, w, 3))
 
     def sliced(self, index):
-        return PendingCoefficientInputs(self.emitter, self.images[index], self.windows[index], self.flips[index])
+        return PendingCoefficientInputs(self.emitter, self.images[index], self.windows[index], self.flips[index], _count=False)
 
     def emit_into(self, buffers):
         """One copy and one launch on the current stream, writing every element of `buffers`: float32 CUDA tensors of
@@ -247,11 +389,27 @@ class DeviceCoefficientInputs(ds.StagingBuffers):
     """Stands where a generator would decode a pre-sized file, crop it and encode it again: the generator thread reads
     bytes and headers and draws, and the file's own coefficients reach the model's inputs through the `StagingBuffers` kept
     here (two pinned buffers used in turn, the event behind the copy, the device blob grown on demand).  `n_threads`: host
-    threads that entropy-decode a batch (None: `StagedPlan.fill`'s default)."""
+    threads that entropy-decode a batch (None: `StagedPlan.fill`'s default).  `device_entropy`: batches whose files all carry
+    restart intervals are entropy-decoded on the GPU (no host thread, the files' bytes are what goes up); `host_batches`
+    counts the batches that took the host path instead.  A segment that fails on the GPU cannot raise where the batch is
+    emitted without a stall: its status reaches the host behind the batch, and the ValueError naming the file is raised
+    when the staging slot is next used, or by `check`."""
 
-    def __init__(self, deconv=False, n_threads=None):
+    def __init__(self, deconv=False, n_threads=None, device_entropy=False):
         self.deconv = bool(deconv)
+        self.device_entropy = bool(device_entropy)
+        self.host_batches = 0
         ds.StagingBuffers.__init__(self, n_threads)
+
+    def check(self, device=None):
+        """Wait for what was emitted on `device` (None: every device used) and raise the ValueError of a batch whose
+        entropy decoding failed there.  For the end of a sweep, a tool or a test."""
+        import torch
+        for name in ([str(torch.device(device))] if device is not None else list(self._state)):
+            if name in self._state:
+                torch.cuda.synchronize(torch.device(name))
+                for slot in self._state[name]["slots"]:
+                    self._check_slot(slot)
 
     def __call__(self, files, windows=None, flips=None):
         return PendingCoefficientInputs(self, files, windows, flips)

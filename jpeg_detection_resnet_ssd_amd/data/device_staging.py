@@ -413,7 +413,9 @@ class StagingBuffers(object):
     """The buffers of whoever stages plans, kept per device and grown on demand: two pinned staging buffers used in turn,
     each refilled only after the upload that last read it has finished (an event recorded behind the copy), the device
     copy of the staging buffer, the scratch of the horizontal pass and the uint8 batch.  `n_threads`: host threads
-    `StagedPlan.fill` reads coefficient planes with (None: its default)."""
+    `StagedPlan.fill` reads coefficient planes with (None: its default).  A plan whose kernels report per-item statuses
+    (`n_status`, `status_view`, `failures`) has them copied to a pinned array of the slot in front of the slot's event;
+    they are read, and a failure raised as ValueError, when the slot is next used (`_check_slot`)."""
 
     def __init__(self, n_threads=None):
         self.n_threads = None if n_threads is None else int(n_threads)
@@ -436,12 +438,14 @@ class StagingBuffers(object):
         kernels write a model's input buffers themselves); it is returned."""
         import torch
         device = torch.device(device)
-        st = self._state.setdefault(str(device), {"slots": [[None, None], [None, None]], "turn": 0, "blob": None,
-                                                  "scratch": None, "out": None})
+        # a slot: [pinned staging buffer, event, pinned int32 statuses, (plan, images) whose statuses are on their way]
+        st = self._state.setdefault(str(device), {"slots": [[None, None, None, None], [None, None, None, None]], "turn": 0,
+                                                  "blob": None, "scratch": None, "out": None})
         slot = st["slots"][st["turn"]]
         st["turn"] ^= 1
         if slot[1] is not None:
             slot[1].synchronize()          # the copy that last read this staging buffer
+            self._check_slot(slot)
         n_out = int(np.prod(plan.out_shape))
         slot[0] = self._grown(slot[0], plan.nbytes)
         for name, n in (("blob", plan.nbytes), ("scratch", plan.scratch_bytes), ("out", n_out)):
@@ -451,11 +455,31 @@ class StagingBuffers(object):
         st["blob"][:plan.nbytes].copy_(slot[0][:plan.nbytes], non_blocking=True)
         if slot[1] is None:
             slot[1] = torch.cuda.Event()
-        slot[1].record()
+        n_status = getattr(plan, "n_status", 0)
+        if not n_status:
+            slot[1].record()
         if out is None:
             out = st["out"][:n_out].view(plan.out_shape)
         plan.launch(host, st["blob"], out, st["scratch"])
+        if n_status:
+            # the kernels' per-segment statuses follow the batch to the slot's pinned array, in front of the slot's event:
+            # nothing waits here, and whoever next waits for the event (the slot's reuse, `check`) reads them
+            if slot[2] is None or slot[2].numel() < n_status:
+                slot[2] = torch.empty(max(n_status, 1024), dtype=torch.int32).pin_memory()
+            slot[2][:n_status].copy_(plan.status_view(st["scratch"]), non_blocking=True)
+            slot[3] = (plan, images)
+            slot[1].record()
         return out
+
+    @staticmethod
+    def _check_slot(slot):
+        """After the slot's event: raise ValueError for the batch last emitted through it if a kernel reported a failure."""
+        if slot[3] is None:
+            return
+        (plan, images), slot[3] = slot[3], None
+        text = plan.failures(slot[2].numpy(), images)
+        if text is not None:
+            raise ValueError(text)
 
 
 class ResidentBuffers(StagingBuffers):

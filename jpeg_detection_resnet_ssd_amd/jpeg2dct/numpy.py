@@ -25,6 +25,43 @@ class JpegDecodeInfo(ctypes.Structure):   # dj_jpeg_decode_info
                 ("device_decodable", ctypes.c_int)]
 
 
+HUFF_BYTES = 896      # DJ_JPEG_HUFF_BYTES
+
+
+class JpegSegmentInfo(ctypes.Structure):   # dj_jpeg_segment_info
+    _fields_ = [("decode", JpegDecodeInfo), ("entropy_decodable", ctypes.c_int), ("reason", ctypes.c_char * 100),
+                ("restart_interval", ctypes.c_int), ("mcus_x", ctypes.c_int), ("mcus_y", ctypes.c_int),
+                ("h_blocks", ctypes.c_int * 4), ("v_blocks", ctypes.c_int * 4), ("dc_table", ctypes.c_int * 4),
+                ("ac_table", ctypes.c_int * 4), ("n_tables", ctypes.c_int), ("n_segments", ctypes.c_int),
+                ("tables", (ctypes.c_ubyte * HUFF_BYTES) * 4)]
+
+
+class SegmentScan(object):
+    """What `scan_segments` found: `entropy_decodable` and, when it is False, `reason`; for an eligible file
+    `restart_interval`, `mcus` = (down, across), per component `grids` [(blocks_h, blocks_w)], `mcu_blocks` [(down,
+    across)] and `dc_table` / `ac_table` (indexes into `tables`), `tables` (n_tables, HUFF_BYTES) uint8 in the device
+    form of include/dj_jpeg_segments.h, and `ranges` (n_segments, 2) int64: [begin, end) of each segment's bytes in the file."""
+
+    def __init__(self, inf, ranges):
+        self.entropy_decodable = bool(inf.entropy_decodable)
+        self.reason = inf.reason.decode(errors="replace")
+        b = inf.decode.base
+        n = self.n_components = int(b.n_components)
+        self.restart_interval = int(inf.restart_interval)
+        self.mcus = (int(inf.mcus_y), int(inf.mcus_x))
+        self.grids = [(int(b.blocks_h[c]), int(b.blocks_w[c])) for c in range(n)]
+        self.mcu_blocks = [(int(inf.v_blocks[c]), int(inf.h_blocks[c])) for c in range(n)]
+        self.dc_table = [int(inf.dc_table[c]) for c in range(n)]
+        self.ac_table = [int(inf.ac_table[c]) for c in range(n)]
+        self.tables4 = _np.frombuffer(inf.tables, dtype=_np.uint8).reshape(4, HUFF_BYTES).copy()      # unused ones zero
+        self.tables = self.tables4[:int(inf.n_tables)]
+        self.ranges = ranges
+
+    @property
+    def n_segments(self):
+        return len(self.ranges)
+
+
 def _lib():
     global _LIB
     if _LIB is None:
@@ -49,6 +86,9 @@ def _lib():
         lib.dj_jpeg_read_raw_batch.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_long), ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_int]
+        lib.dj_jpeg_scan_segments.restype = ctypes.c_int
+        lib.dj_jpeg_scan_segments.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.POINTER(JpegSegmentInfo), ctypes.c_void_p,
+                                              ctypes.c_long]
         _LIB = lib
     return _LIB
 
@@ -73,6 +113,24 @@ def decode_info(buf):
     inf = JpegDecodeInfo()
     _check(_lib().dj_jpeg_read_decode_info(buf, len(buf), ctypes.byref(inf)))
     return inf
+
+
+def scan_segments(buf, max_segments=None):
+    """The pre-pass of entropy decoding on the GPU (include/dj_jpeg_segments.h: dj_jpeg_scan_segments): headers and one
+    search for 0xFF bytes, no Huffman decoding -> `SegmentScan`.  A file that is not eligible -- one the reader cannot
+    parse included -- comes back with `entropy_decodable` False and a `reason`, never as an exception.  `max_segments`: an
+    upper bound the caller knows (the file's MCU count), which saves the first of two calls."""
+    buf = bytes(buf)
+    inf = JpegSegmentInfo()
+    if len(buf) == 0:
+        inf.reason = b"empty file"
+        return SegmentScan(inf, _np.zeros((0, 2), dtype=_np.int64))
+    ranges = _np.zeros((int(max_segments or 0), 2), dtype=_np.int64)
+    _check(_lib().dj_jpeg_scan_segments(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
+    if inf.n_segments > len(ranges):
+        ranges = _np.zeros((inf.n_segments, 2), dtype=_np.int64)
+        _check(_lib().dj_jpeg_scan_segments(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
+    return SegmentScan(inf, ranges[:inf.n_segments].copy())
 
 
 def default_threads():

@@ -619,6 +619,8 @@ class Model(object):
             if feeder is not None:
                 feeder.close()
         values = sweep.finish()
+        if hasattr(generator, "check_inputs"):      # a failure a device input path only finds behind the batch
+            generator.check_inputs()
         out = [values[name] for name in self.metrics_names]
         if verbose:
             print("%d/%d - %.0fs - %s" % (steps, steps, time.time() - t0,
@@ -688,6 +690,9 @@ class Model(object):
                     sweep.add(validation_data[0], validation_data[1])
                 for mk, mv in sweep.finish().items():
                     logs["val_" + mk] = mv
+            for source in (generator, validation_data):
+                if hasattr(source, "check_inputs"):      # a failure a device input path only finds behind the batch
+                    source.check_inputs()
             if self.dist is not None:
                 logs = self.dist.average_metrics(logs)
             if verbose and rank0:

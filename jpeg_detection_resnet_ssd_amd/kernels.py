@@ -555,6 +555,38 @@ def jpeg_dct_inputs(coef, desc_dev, desc_host, tables_dev, tables_host, outs, st
     return outs
 
 
+# ---- Huffman entropy decoding of restart-interval files: one lane per restart interval -----------------------------------------
+def jpeg_entropy_decode(data, desc_dev, desc_host, seg_dev, seg_host, tables_dev, tables_host, out, status, stream=None):
+    """dj_jpeg_entropy_decode: `data` the 1-D uint8 CUDA tensor holding the files' bytes, `desc_dev` / `seg_dev` the file
+    descriptors' and segment records' bytes on the device and `desc_host` / `seg_host` the same as numpy arrays of
+    data/coefficient_inputs.py:ENTROPY_DTYPE / SEGMENT_DTYPE, `tables_dev` the Huffman tables' bytes on the device (1-D
+    uint8) and `tables_host` the same as an (n_tables, 896) uint8 numpy array (only its shape is read), `out` the 1-D
+    uint8 CUDA tensor the raw int16 planes are written into where the descriptors say (every element of every plane),
+    `status` an int32 CUDA tensor that receives one status per segment.  `stream`: a HIP stream handle (None: the current
+    launch stream)."""
+    import ctypes
+    import numpy as np
+    from ._lib import JpegEntropyDesc, JpegEntropySeg
+    from .data.coefficient_inputs import ENTROPY_DTYPE, SEGMENT_DTYPE
+    from .jpeg2dct.numpy import HUFF_BYTES
+    n = _check_staged(desc_host, ENTROPY_DTYPE, JpegEntropyDesc, desc_dev,
+                      ((data, "data"), (desc_dev, "desc_dev"), (seg_dev, "seg_dev"), (tables_dev, "tables_dev"), (out, "out")))
+    assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(JpegEntropySeg), "segment-record layouts disagree"
+    assert isinstance(seg_host, np.ndarray) and seg_host.dtype == SEGMENT_DTYPE and seg_host.ndim == 1 \
+        and seg_host.flags.c_contiguous, "seg_host: expected a contiguous 1-D array of SEGMENT_DTYPE"
+    assert seg_dev.numel() >= seg_host.nbytes and seg_dev.data_ptr() % 8 == 0, "seg_dev: too small or misaligned"
+    assert isinstance(tables_host, np.ndarray) and tables_host.dtype == np.uint8 and tables_host.ndim == 2 \
+        and tables_host.shape[1] == HUFF_BYTES, "tables_host: expected an (n_tables, %d) uint8 array" % HUFF_BYTES
+    assert tables_dev.numel() >= tables_host.size, "tables_dev: smaller than the tables"
+    assert status.is_cuda and status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous() \
+        and status.numel() >= seg_host.shape[0], "status: expected a contiguous int32 CUDA tensor of one entry per segment"
+    check(_L().dj_jpeg_entropy_decode(ptr(data), data.numel(), ptr(desc_dev), desc_host.ctypes.data, n, ptr(seg_dev),
+                                      seg_host.ctypes.data, seg_host.shape[0], ptr(tables_dev), tables_host.shape[0],
+                                      ptr(out), out.numel(), ptr(status), stream if stream is not None else _stream()),
+          "dj_jpeg_entropy_decode")
+    return out, status
+
+
 # ---- Pascal-VOC evaluation: greedy matching, then cumulative counts / precision / recall / sampled AP -------------------------
 def _check_eval_tensor(t, name, dtype, numel):
     assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel, \

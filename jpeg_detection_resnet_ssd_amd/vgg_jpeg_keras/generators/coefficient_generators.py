@@ -11,7 +11,10 @@ origin and `random.randint(0, width // 16 - T // 16)` the column origin of a T x
 ValueError naming its path: files are expected to be pre-sized (tools/presize_dataset.py).
 
 `device=True` returns `(PendingCoefficientInputs, y)`: the entropy decoding runs on `decode_threads` host threads and the
-window, mirror and de-quantisation on the GPU when the model uploads the batch.  `device=False` returns the host statement's
+window, mirror and de-quantisation on the GPU when the model uploads the batch.  `device_entropy=True` on top of it: a
+batch whose files all carry restart intervals (tools/presize_dataset.py --restart-rows / --restart-mcus) is entropy-decoded
+on the GPU too, from the files' bytes, with no host thread; any other batch takes the host threads (`host_batches` counts
+them).  `device=False` returns the host statement's
 arrays.  Both make the same draws and leave `random` in the same state."""
 import os
 import random
@@ -28,9 +31,11 @@ class DCTGeneratorCoefficients(Sequence):
     deconv = False
 
     def __init__(self, data_directory, index_file, batch_size=32, shuffle=True, target_length=224, random_crop=True,
-                 flip=True, device=True, decode_threads=None):
+                 flip=True, device=True, decode_threads=None, device_entropy=False):
         if int(target_length) < MCU or int(target_length) % MCU:
             raise ValueError("target_length must be a positive multiple of %d, got %r" % (MCU, target_length))
+        if device_entropy and not device:
+            raise ValueError("device_entropy needs device=True: the files are entropy-decoded where the batch is uploaded")
         self.association, self.classes, self.images_path = prepare_imagenet(index_file, data_directory)
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -42,7 +47,8 @@ class DCTGeneratorCoefficients(Sequence):
         self.number_of_classes = len(self.classes)
         self.batches_per_epoch = len(self.images_path) // self.batch_size
         self.indexes = np.arange(len(self.images_path))
-        self._emit = DeviceCoefficientInputs(deconv=self.deconv, n_threads=decode_threads) if device else None
+        self._emit = DeviceCoefficientInputs(deconv=self.deconv, n_threads=decode_threads,
+                                             device_entropy=device_entropy) if device else None
         self.on_epoch_end()
 
     def __len__(self):
@@ -63,9 +69,23 @@ class DCTGeneratorCoefficients(Sequence):
         with open(path, "rb") as f:
             data = f.read()
         try:
-            return check_file(data)
+            image = check_file(data)
         except ValueError as e:
             raise ValueError("%s: %s" % (path, e))
+        image.name = path      # for the message of a failure that is only found on the GPU
+        return image
+
+    def check_inputs(self):
+        """Wait for the batches handed to a model and raise the ValueError of one whose entropy decoding failed on the GPU
+        (`device_entropy=True`: such a failure is found behind the batch).  `evaluate_generator` and `fit_generator` call
+        it when a sweep or an epoch ends."""
+        if self._emit is not None:
+            self._emit.check()
+
+    @property
+    def host_batches(self):
+        """Batches that `device_entropy=True` could not take because a file had no restart intervals."""
+        return self._emit.host_batches if self._emit is not None else 0
 
     def _draws(self, path, height, width):
         """-> ((y0, x0, T, T), mirror) of one image, drawn from `random` in the module's order."""

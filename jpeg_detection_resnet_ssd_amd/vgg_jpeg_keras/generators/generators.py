@@ -62,14 +62,24 @@ def device_switches(environ=os.environ):
 def coefficient_switch(environ=os.environ):
     """Whether the configurations feed the DCT architectures the files' own coefficients
     (coefficient_generators.py): `DJ_COEFFICIENT_INPUTS=1`.  That path has no pixels to prepare or distort, so combining it
-    with `DJ_DEVICE_PREP`, `DJ_DEVICE_DECODE` or `DJ_PHOTOMETRIC` is a ValueError."""
+    with `DJ_DEVICE_PREP`, `DJ_DEVICE_DECODE` or `DJ_PHOTOMETRIC` is a ValueError.  `DJ_DEVICE_ENTROPY=1`
+    (`device_entropy_switch`) belongs to this path alone: without `DJ_COEFFICIENT_INPUTS=1` it is a ValueError."""
     if environ.get("DJ_COEFFICIENT_INPUTS", "0") != "1":
+        if environ.get("DJ_DEVICE_ENTROPY", "0") == "1":
+            raise ValueError("DJ_DEVICE_ENTROPY=1 needs DJ_COEFFICIENT_INPUTS=1: only the coefficient path entropy-decodes "
+                             "on the GPU")
         return False
     clash = [k for k in ("DJ_DEVICE_PREP", "DJ_DEVICE_DECODE", "DJ_PHOTOMETRIC") if environ.get(k, "0") == "1"]
     if clash:
         raise ValueError("DJ_COEFFICIENT_INPUTS=1 cannot be combined with %s: the files' own coefficients are fed to the "
                          "model, there are no pixels to prepare or distort" % ", ".join(clash))
     return True
+
+
+def device_entropy_switch(environ=os.environ):
+    """Whether the coefficient generators entropy-decode restart-interval files on the GPU: `DJ_DEVICE_ENTROPY=1`, which
+    needs `DJ_COEFFICIENT_INPUTS=1` (ValueError without it)."""
+    return coefficient_switch(environ) and environ.get("DJ_DEVICE_ENTROPY", "0") == "1"
 
 
 class DCTGeneratorJPEG2DCT(Sequence):

@@ -10,6 +10,13 @@
   (c) the files' own coefficients: DCTGeneratorCoefficients(device=True) -- entropy decode on 16 host threads, then
       dj_jpeg_dct_inputs.  The same breakdown as (a), the kernel alone over 50 launches back to back, and its bytes moved
       (2 read and 4 written per coefficient, plus tables and descriptors) over that time
+  (d) the same, entropy-decoded on the GPU: the same 64 images written with one restart interval per MCU row
+      (`restart_marker_rows=1`) and fed by DCTGeneratorCoefficients(device=True, device_entropy=True) -- the files' bytes go
+      up, dj_jpeg_entropy_decode makes the raw planes in device scratch, dj_jpeg_dct_inputs reads them.  Beside it, in
+      the same session, (c) on those same restart-interval files with 16 host threads and with 1, which is the
+      yardstick; (d)'s outputs are asserted equal to (c)'s.  `emit_into`, fill, bytes uploaded, the entropy kernel by
+      events and over 50 launches back to back, and what the markers add to the files; then all of it again for
+      `restart_marker_blocks=4` (four times the segments, more marker bytes)
 
     python tools/coefficient_rate.py [--reps 20]
 
@@ -65,8 +72,9 @@ def event_ms(fn, reps, launches=1):
     return statistics.median(times), min(times), max(times)
 
 
-def write_tree(root, rng):
-    """64 files of 256x256 in one class directory: smooth content plus noise, saved at quality 90 (PIL's 4:2:0)."""
+def write_tree(root, rng, **save):
+    """64 files of 256x256 in one class directory: smooth content plus noise, saved at quality 90 (PIL's 4:2:0); `save`:
+    further arguments of PIL's JPEG writer (the restart interval)."""
     from PIL import Image
     directory = os.path.join(root, "train", "n_all")
     os.makedirs(directory)
@@ -75,7 +83,7 @@ def write_tree(root, rng):
     for i in range(B):
         img = np.stack([127 + 100 * np.sin(xx / (11.0 + c + i % 7) + c) * np.cos(yy / (8.0 + 2 * c)) for c in range(3)], axis=-1)
         buf = io.BytesIO()
-        Image.fromarray(np.clip(img + rng.normal(0, 15, img.shape), 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90)
+        Image.fromarray(np.clip(img + rng.normal(0, 15, img.shape), 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90, **save)
         files.append(buf.getvalue())
         with open(os.path.join(directory, "img%03d.jpg" % i), "wb") as f:
             f.write(files[-1])
@@ -101,6 +109,50 @@ def generator_rows(res, key, gen, bufs, reps):
     res[key + "_emit_only_ms"] = median_ms(lambda: pending.emit_into(bufs), reps)
     res[key + "_blob_MB"] = pending.plan.nbytes / 1e6
     return pending
+
+
+def entropy_rows(res, key, root, plain_bytes, bufs, reps, dev, **restart):
+    """Rows (c) and (d) on the 64 images written with the restart interval `restart`, keys prefixed `key`."""
+    from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import DCTGeneratorCoefficients
+    directory, index_file, files = write_tree(os.path.join(root, key), np.random.default_rng(0), **restart)
+    res[key + "_files_MB"] = sum(len(f) for f in files) / 1e6
+    res[key + "_file_growth_percent"] = 100.0 * (sum(len(f) for f in files) / plain_bytes - 1.0)
+
+    def generator(**kw):
+        return DCTGeneratorCoefficients(directory, index_file, batch_size=B, shuffle=False, target_length=T, device=True, **kw)
+    # (c) on these files: host entropy decoding on 16 threads and on 1
+    for name, threads in (("c16", THREADS), ("c1", 1)):
+        pending = generator_rows(res, key + "_" + name, generator(decode_threads=threads), bufs, reps)
+        staging = torch.empty(pending.plan.nbytes, dtype=torch.uint8).pin_memory()
+        res[key + "_" + name + "_fill_ms"] = median_ms(lambda: pending.plan.fill(staging.numpy(), pending.images, threads), reps)
+    pending.emit_into(bufs)
+    torch.cuda.synchronize()
+    want = [b.clone() for b in bufs]
+    # (d) entropy decoding on the GPU
+    gen_d = generator(decode_threads=THREADS, device_entropy=True)
+    pending_d = generator_rows(res, key + "_d", gen_d, bufs, reps)
+    gen_d.check_inputs()
+    assert gen_d.host_batches == 0, "every batch must take the device path"
+    res[key + "_d_equals_c"] = all(bool((b == w).all()) for b, w in zip(bufs, want))
+    assert res[key + "_d_equals_c"], "device_entropy=True and the host reader disagree"
+    plan = pending_d.plan
+    res[key + "_segments"] = plan.n_status
+    staging, blob = staged(plan, pending_d.images, dev)
+    host = staging.numpy()
+    res[key + "_d_fill_ms"] = median_ms(lambda: plan.fill(host, pending_d.images), reps)
+    res[key + "_d_upload_ms"] = median_ms(lambda: blob.copy_(staging, non_blocking=True), reps)
+    scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
+    edesc_h, segs_h, huff_h, _ = plan.entropy_views(host)
+    edesc_d, segs_d, huff_d, bytes_d = plan.entropy_views(blob)
+
+    def entropy():
+        kernels.jpeg_entropy_decode(bytes_d, edesc_d, edesc_h, segs_d, segs_h, huff_d, huff_h, scratch[:plan.coef_bytes],
+                                    plan.status_view(scratch))
+    res[key + "_d_entropy_kernel_ms"] = event_ms(entropy, max(50, reps))
+    res[key + "_d_entropy_kernel_50_back_to_back_ms"] = event_ms(entropy, reps, launches=50)
+    res[key + "_d_both_kernels_ms"] = event_ms(lambda: plan.launch(host, blob, bufs, scratch), max(50, reps))
+    torch.cuda.synchronize()
+    assert not plan.status_view(scratch).any().item()
 
 
 def main():
@@ -164,6 +216,11 @@ def main():
         res["c_kernel_bytes"] = 6 * coefficients + plan_c.tables.nbytes + plan_c.desc.nbytes
         res["c_kernel_GBs"] = res["c_kernel_bytes"] / res["c_kernel_50_back_to_back_ms"][0] / 1e6
 
+        # (d) entropy decoding on the GPU, beside (c) on the same restart-interval files
+        plain_bytes = sum(len(f) for f in files)
+        entropy_rows(res, "rows1", root, plain_bytes, bufs, reps, dev, restart_marker_rows=1)
+        entropy_rows(res, "mcus4", root, plain_bytes, bufs, reps, dev, restart_marker_blocks=4)
+
     def cell(v):
         return "%.2f (%.2f - %.2f)" % tuple(v) if isinstance(v, tuple) else ("%.2f" % v if isinstance(v, float) else str(v))
     rows = [("files on disk to input tensors: `gen[0]` + `emit_into` (ms)", "a_batch_and_emit_ms", None, "c_batch_and_emit_ms"),
@@ -180,6 +237,19 @@ def main():
     print("|---|---|---|---|")
     for name, a, b, c in rows:
         print("| %s | %s | %s | %s |" % ((name,) + tuple("-" if k is None else cell(res[k]) for k in (a, b, c))))
+    print()
+    print("| restart-interval files | (c) 16 host threads | (c) 1 host thread | (d) device_entropy |")
+    print("|---|---|---|---|")
+    for key, label in (("rows1", "one interval per MCU row"), ("mcus4", "one interval per 4 MCUs")):
+        print("| **%s**: %d segments, files %.2f MB (+%.2f %%) | | | |"
+              % (label, res[key + "_segments"], res[key + "_files_MB"], res[key + "_file_growth_percent"]))
+        for name, suffix in (("`gen[0]` + `emit_into` (ms)", "_batch_and_emit_ms"), ("`emit_into` (ms)", "_emit_only_ms"),
+                             ("fill (ms)", "_fill_ms"), ("bytes uploaded (MB)", "_blob_MB")):
+            print("| %s | %s | %s | %s |" % ((name,) + tuple(cell(res[key + "_" + col + suffix]) for col in ("c16", "c1", "d"))))
+        for name, k in (("upload from pinned memory (ms)", "_d_upload_ms"), ("dj_jpeg_entropy_decode by events (ms)", "_d_entropy_kernel_ms"),
+                        ("dj_jpeg_entropy_decode, 50 launches back to back (ms each)", "_d_entropy_kernel_50_back_to_back_ms"),
+                        ("both kernels by events (ms)", "_d_both_kernels_ms")):
+            print("| %s | - | - | %s |" % (name, cell(res[key + k])))
     print(json.dumps(res), flush=True)
 
 

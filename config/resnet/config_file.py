@@ -19,6 +19,9 @@ as well, for every generator above: files travel as entropy-decoded coefficients
 `DJ_COEFFICIENT_INPUTS=1` (with none of the three switches above, else an error) feeds the DCT architectures pre-sized
 baseline 4:2:0 files as their OWN coefficients instead (vgg_jpeg_keras/generators/coefficient_generators.py): a random
 window of whole MCUs and a lossless mirror for training, the centred window for validation and test.
+`DJ_DEVICE_ENTROPY=1` on top of it entropy-decodes batches of restart-interval files on the GPU, and
+`DJ_DEVICE_ENTROPY_UNMARKED=1` on top of that (an error without it) batches with files that carry no restart intervals, by
+chunks (vgg_jpeg_keras/generators: `device_entropy_switch`, `unmarked_switch`).
 `prepare_horovod(hvd)` reproduces the reference's data-parallel scaling rules (:121-150) with `hvd` = the RCCL adapter
 of training.py."""
 from os import environ
@@ -34,7 +37,8 @@ from jpeg_detection_resnet_ssd_amd.keras.metrics import top_k_categorical_accura
 from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD
 from jpeg_detection_resnet_ssd_amd.keras.utils import Sequence
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.evaluation import Evaluator
-from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import coefficient_switch, device_entropy_switch, device_switches
+from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import (coefficient_switch, device_entropy_switch, device_switches,
+                                                                     unmarked_switch)
 from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.networks.resnet_dct import ResNet50Custom, ResNet50RGB
 
 
@@ -186,7 +190,7 @@ class TrainingConfiguration(object):
         cls = DCTGeneratorCoefficientsDeconv if self.deconv else DCTGeneratorCoefficients
         return cls(directory, index_file, self._batch_size, target_length=self.img_size[0], random_crop=training,
                    flip=training, decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")),
-                   device_entropy=device_entropy_switch())
+                   device_entropy=device_entropy_switch(), unmarked=unmarked_switch())
 
     def _rgb_generator(self, directory, training):
         """The reference's two calls for the RGB ResNet50 (classification_part/config/resnetRGB/config_file.py:157-172)."""

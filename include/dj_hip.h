@@ -682,12 +682,30 @@ typedef struct dj_jpeg_entropy_seg {
   long begin, end;                 /* bytes */
   int file;
   int first_mcu, n_mcus;
-  int reserved;
+  int reserved;                    /* dj_jpeg_entropy_decode_chunked: the segment's first chunk; otherwise unused */
 } dj_jpeg_entropy_seg;
 int dj_jpeg_entropy_decode(const unsigned char* bytes, long n_bytes, const dj_jpeg_entropy_desc* desc_dev,
                            const dj_jpeg_entropy_desc* desc_host, int n_files, const dj_jpeg_entropy_seg* seg_dev,
                            const dj_jpeg_entropy_seg* seg_host, int n_segments, const unsigned char* tables, int n_tables,
                            unsigned char* out, long out_bytes, int* status, void* stream);
+
+/* ---- The same planes and statuses for files WITHOUT restart intervals (and for files with them), by chunks: a segment is
+ * cut every `chunk_bytes` raw bytes (a multiple of 16 in 16..4096; at most 65536 chunks a segment), the chunks are decoded
+ * in parallel from guessed states and synchronised by a bounded fixed-point iteration whose result is the sequential
+ * decode -- data/entropy_decode.py:chunked_decode_host states the scheme, csrc/dj_jpeg_entropy_chunked.hip runs it.  The
+ * host half is dj_jpeg_scan_segments_unmarked (include/dj_jpeg_segments.h).
+ * Arguments, checks and guarantees of dj_jpeg_entropy_decode, and in addition: record s's `reserved` is the number of
+ * chunks of the segments in front of it (segment s has max(1, ceil((end - begin) / chunk_bytes)) chunks); `scratch` is a
+ * DEVICE buffer, 16-byte aligned, of at least dj_jpeg_entropy_chunked_scratch_bytes(chunks, files, segments, blocks) bytes
+ * (blocks: the sum over the files of mcus_x * mcus_y * blocks per MCU), whose contents need not survive between calls;
+ * `rounds` (DEVICE, may be null) receives per segment the synchronisation rounds it took, at most its chunk count.
+ * Five launches on `stream`, no synchronisation: capturable. ---- */
+long dj_jpeg_entropy_chunked_scratch_bytes(long n_chunks, long n_files, long n_segments, long n_blocks);
+int dj_jpeg_entropy_decode_chunked(const unsigned char* bytes, long n_bytes, const dj_jpeg_entropy_desc* desc_dev,
+                                   const dj_jpeg_entropy_desc* desc_host, int n_files, const dj_jpeg_entropy_seg* seg_dev,
+                                   const dj_jpeg_entropy_seg* seg_host, int n_segments, const unsigned char* tables, int n_tables,
+                                   unsigned char* out, long out_bytes, int* status, int chunk_bytes, unsigned char* scratch,
+                                   long scratch_bytes, int* rounds, void* stream);
 
 /* ---- Pascal-VOC evaluation (L/eval_utils/average_precision_evaluator.py:570-925): `Evaluator.match_predictions`,
  * `compute_precision_recall` and `compute_average_precisions(mode='sample')` with results equal bit for bit to the host

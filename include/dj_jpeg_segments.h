@@ -45,6 +45,15 @@ typedef struct dj_jpeg_segment_info {
 int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
                           long range_capacity);
 
+/* ---- The same pre-pass for files without restart intervals as well (data/entropy_decode.py:chunked_decode_host states how
+ * they are decoded in parallel, csrc/dj_jpeg_entropy_chunked.hip runs it).  Same arguments, same conditions and the same
+ * output for every file dj_jpeg_scan_segments accepts; in addition a file with no DRI segment (or DRI 0) is eligible when
+ * its entropy-coded data holds no FF xx but FF 00 before EOI: it reports restart_interval = mcus_x * mcus_y and ONE segment,
+ * the scan's entropy-coded bytes.  It never decodes a Huffman code either, never fails for a file's content and refuses
+ * every proper prefix of a file. ---- */
+int dj_jpeg_scan_segments_unmarked(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
+                                   long range_capacity);
+
 #ifdef __cplusplus
 }
 #endif

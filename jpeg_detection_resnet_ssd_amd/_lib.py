@@ -220,6 +220,9 @@ SIGNATURES = {
                                    FP, c_long, c_long, FP, c_long, c_long, FP, c_long, c_long, c_void_p]),
     "dj_jpeg_entropy_decode": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p, c_long, c_void_p, c_void_p]),
+    "dj_jpeg_entropy_chunked_scratch_bytes": (c_long, [c_long, c_long, c_long, c_long]),
+    "dj_jpeg_entropy_decode_chunked": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                               c_int, c_void_p, c_long, c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "dj_eval_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
                               c_void_p]),

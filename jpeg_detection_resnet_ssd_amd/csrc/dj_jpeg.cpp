@@ -653,7 +653,8 @@ void device_table(const Huff& h, unsigned char* out) {
   memcpy(out, lut, 512);
   memcpy(out + 512, limit, 64);
   memcpy(out + 576, offset, 64);
-  memcpy(out + 640, h.vals, 256);
+  memset(out + 640, 0, 256);      // the symbols the table defines, zeros behind them: the same bytes on every call
+  memcpy(out + 640, h.vals, (size_t)(k < 256 ? k : 256));
 }
 
 int not_eligible(dj_jpeg_segment_info* info, const char* fmt, ...) {
@@ -666,10 +667,9 @@ int not_eligible(dj_jpeg_segment_info* info, const char* fmt, ...) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
-                                     long range_capacity) {
+// the pre-pass of both entry points; `unmarked`: a file without restart intervals is one segment of all its MCUs
+int scan_segments(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges, long range_capacity,
+                  bool unmarked) {
   if (!data || !info || size <= 0 || (range_capacity > 0 && !ranges)) return fail("scan_segments: null argument");
   memset(info, 0, sizeof(*info));
   Decoder d;
@@ -710,12 +710,13 @@ extern "C" int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jp
   info->n_tables = n_tables;
   const unsigned char* tail = hdr + 1 + 2 * ns;
   if (tail[0] != 0 || tail[1] != 63 || tail[2] != 0) return not_eligible(info, "not a sequential scan");
-  if (d.restart_interval <= 0) return not_eligible(info, "no restart interval (DRI)");
-  info->restart_interval = d.restart_interval;
+  if (d.restart_interval <= 0 && !unmarked) return not_eligible(info, "no restart interval (DRI)");
   info->mcus_x = ns == 1 ? d.comp[0].blocks_w : (d.width + 8 * d.hmax - 1) / (8 * d.hmax);
   info->mcus_y = ns == 1 ? d.comp[0].blocks_h : (d.height + 8 * d.vmax - 1) / (8 * d.vmax);
   const long n_mcus = (long)info->mcus_x * info->mcus_y;
-  const long n_segments = (n_mcus + d.restart_interval - 1) / d.restart_interval;
+  const long interval = d.restart_interval > 0 ? d.restart_interval : n_mcus;
+  info->restart_interval = (int)interval;
+  const long n_segments = (n_mcus + interval - 1) / interval;
   // one linear search for 0xFF from the scan's first byte to EOI
   const bool keep = range_capacity >= n_segments;
   long seen = 0;
@@ -743,6 +744,18 @@ extern "C" int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jp
   info->n_segments = (int)n_segments;
   info->entropy_decodable = 1;
   return 0;
+}
+
+}  // namespace
+
+extern "C" int dj_jpeg_scan_segments(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
+                                     long range_capacity) {
+  return scan_segments(data, size, info, ranges, range_capacity, false);
+}
+
+extern "C" int dj_jpeg_scan_segments_unmarked(const unsigned char* data, long size, dj_jpeg_segment_info* info, long* ranges,
+                                              long range_capacity) {
+  return scan_segments(data, size, info, ranges, range_capacity, true);
 }
 
 extern "C" int dj_jpeg_read_raw_batch(const unsigned char* const* data, const long* sizes, int n, unsigned char* buffer,

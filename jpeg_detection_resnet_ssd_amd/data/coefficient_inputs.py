@@ -28,7 +28,10 @@ Entropy decoding on the GPU (opt-in, `DeviceCoefficientInputs(device_entropy=Tru
 intervals (jpeg2dct/numpy.py:`scan_segments` decides) uploads the files' bytes instead of their planes, and
 csrc/dj_jpeg_entropy.hip (`kernels.jpeg_entropy_decode`) makes the same raw planes in device scratch, one restart interval
 per lane, as data/entropy_decode.py states; any other batch takes the host reader whole.  The numbers that reach the model
-are the same bit for bit.
+are the same bit for bit.  `unmarked=True` on top of it widens that to ordinary files, which carry no restart intervals: a
+batch that the one-lane-per-interval kernel cannot take, but whose files all pass the wider pre-pass
+(`scan_segments(unmarked=True)`), is decoded by chunks (`ChunkedEntropyCoefficientPlan`, csrc/dj_jpeg_entropy_chunked.hip,
+data/entropy_decode.py:`chunked_decode_host`), marked files riding along as several short segments.
 
 All arithmetic here is int32 / int16."""
 import numpy as np
@@ -228,13 +231,19 @@ SEGMENT_DTYPE = np.dtype([("begin", np.int64), ("end", np.int64), ("file", np.in
                           ("n_mcus", np.int32), ("reserved", np.int32)], align=True)
 
 
-def segment_scan(image):
+def segment_scan(image, unmarked=False):
     """The pre-pass's verdict and findings for a `CoefficientImage` (jpeg2dct/numpy.py:`scan_segments`), made once per
-    file where its header is parsed and kept on the image."""
+    file where its header is parsed and kept on the image.  `unmarked`: the wider pre-pass, which a file without restart
+    intervals passes as one segment; it is run only for a file that fails the other one, whose findings it repeats
+    otherwise."""
     scan = getattr(image, "_segment_scan", None)
     if scan is None:
         bh, bw = image.grids()[0]
         scan = image._segment_scan = reader.scan_segments(image.data, max_segments=bh * bw)
+    if unmarked and not scan.entropy_decodable:
+        scan = getattr(image, "_segment_scan_unmarked", None)
+        if scan is None:
+            scan = image._segment_scan_unmarked = reader.scan_segments(image.data, max_segments=1, unmarked=True)
     return scan
 
 
@@ -346,6 +355,77 @@ class EntropyCoefficientPlan(CoefficientPlan):
         return "entropy decoding on the GPU failed for " + "; ".join(bad)
 
 
+DEFAULT_CHUNK_BYTES = 512      # the lowest kernel time of 64 / 128 / 256 / 512 on the measured batch
+
+
+def chunk_counts(segments, chunk_bytes):
+    """The chunks of every record of a SEGMENT_DTYPE array: max(1, ceil((end - begin) / chunk_bytes))."""
+    return np.maximum(1, -(-(segments["end"] - segments["begin"]) // int(chunk_bytes))).astype(np.int64)
+
+
+def fill_chunks(desc, segs, chunk_bytes):
+    """Write every record's first chunk -- the number of chunks of the records in front of it -- into its `reserved`, as
+    dj_jpeg_entropy_decode_chunked reads it -> (chunks in all, blocks in all: the files' MCUs times their blocks per MCU,
+    MCU padding included)."""
+    counts = chunk_counts(segs, chunk_bytes)
+    segs["reserved"] = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    per_mcu = (desc["h_blocks"] * desc["v_blocks"] * (np.arange(3)[None, :] < desc["n_components"][:, None])).sum(axis=1)
+    return int(counts.sum()), int((desc["mcus_x"].astype(np.int64) * desc["mcus_y"] * per_mcu).sum())
+
+
+def chunked_records(scans, plane_offsets, file_offsets, chunk_bytes):
+    """`entropy_records` with `fill_chunks` applied -> (descriptors, records, tables, chunks in all, blocks in all)."""
+    desc, segs, tables = entropy_records(scans, plane_offsets, file_offsets)
+    return (desc, segs, tables) + fill_chunks(desc, segs, chunk_bytes)
+
+
+def chunked_scratch_bytes(n_chunks, n_files, n_segments, n_blocks):
+    """dj_jpeg_entropy_chunked_scratch_bytes (include/dj_hip.h): chunk records of 32 bytes, a first block per file, a
+    failing block per segment and a DC difference per block, each part rounded up to 16 bytes."""
+    return sum(ds.round_up(n, 16) for n in (32 * n_chunks, 8 * n_files, 4 * n_segments, 2 * n_blocks))
+
+
+class ChunkedEntropyCoefficientPlan(EntropyCoefficientPlan):
+    """The plan of a batch with files that carry no restart intervals, all eligible by `segment_scan(unmarked=True)`: the
+    staging blob of `EntropyCoefficientPlan` (the records' `reserved` holding each segment's first chunk), and a scratch of
+    `[planes | one int32 status per segment | chunk states, first blocks, failing blocks and DC differences]`, the last
+    part at a multiple of 64 bytes, where dj_jpeg_entropy_decode_chunked works (data/entropy_decode.py states the scheme)."""
+
+    def __init__(self, images, windows, flips, grids, scans, chunk_bytes=DEFAULT_CHUNK_BYTES):
+        from .entropy_decode import check_chunk_bytes
+        self.chunk_bytes = check_chunk_bytes(chunk_bytes)
+        EntropyCoefficientPlan.__init__(self, images, windows, flips, grids, scans)
+        # the records are laid out by reference: filling `reserved` here reaches the blob
+        self.n_chunks, self.n_blocks = fill_chunks(self.entropy, self.segments, self.chunk_bytes)
+        self.work_offset = ds.round_up(self.status_offset + 4 * self.n_status)
+        self.work_bytes = chunked_scratch_bytes(self.n_chunks, self.batch, self.n_status, self.n_blocks)
+        self.scratch_bytes = self.work_offset + self.work_bytes
+
+    def launch(self, blob_host, blob_dev, out, scratch=None, stream=None):
+        """dj_jpeg_entropy_decode_chunked into `scratch` (a 1-D uint8 CUDA tensor of at least `scratch_bytes`, 16-byte
+        aligned), then dj_jpeg_dct_inputs from it into `out`."""
+        from .. import kernels
+        if scratch is None or scratch.numel() < self.scratch_bytes:
+            raise ValueError("this plan needs %d bytes of device scratch" % self.scratch_bytes)
+        desc_h, tables_h, _ = self.views(blob_host)
+        desc_d, tables_d, _ = self.views(blob_dev)
+        edesc_h, segs_h, huff_h, _ = self.entropy_views(blob_host)
+        edesc_d, segs_d, huff_d, bytes_d = self.entropy_views(blob_dev)
+        planes = scratch[:self.coef_bytes]
+        kernels.jpeg_entropy_decode_chunked(bytes_d, edesc_d, edesc_h, segs_d, segs_h, huff_d, huff_h, planes,
+                                            self.status_view(scratch), self.chunk_bytes,
+                                            scratch[self.work_offset:self.work_offset + self.work_bytes], stream=stream)
+        outs = tuple(out) if len(out) == 3 else (out[0], out[1][..., :64], out[1][..., 64:])
+        kernels.jpeg_dct_inputs(planes, desc_d, desc_h, tables_d, tables_h, outs, stream=stream)
+        return out
+
+
+def chunkable(scans, chunk_bytes):
+    """Whether every segment of these eligible scans stays within the chunk cap (entropy_decode.MAX_CHUNKS)."""
+    from .entropy_decode import MAX_CHUNKS
+    return all(int((s.ranges[:, 1] - s.ranges[:, 0]).max()) <= MAX_CHUNKS * int(chunk_bytes) for s in scans)
+
+
 class PendingCoefficientInputs(PendingInputs):
     """The files of one batch with their windows and mirrors, on their way into a model's resident input buffers
     (`Model.train_on_batch / predict / fit_generator` accept it where they accept the list of input arrays): at upload time
@@ -353,15 +433,25 @@ class PendingCoefficientInputs(PendingInputs):
     and one launch of dj_jpeg_dct_inputs writes the inputs.  `shape` is that of the pixel batch the windows stand for.
     With an emitter whose `device_entropy` is set and a batch whose files are ALL entropy-decodable on the GPU, the files'
     bytes go up instead and dj_jpeg_entropy_decode makes the planes there (`EntropyCoefficientPlan`); a batch with any
-    other file takes the host path whole, and the emitter's `host_batches` counts it."""
+    other file takes the host path whole, and the emitter's `host_batches` counts it.  With `unmarked` set as well, a batch
+    with files that carry no restart intervals, all eligible by the wider pre-pass and within the chunk cap, takes
+    `ChunkedEntropyCoefficientPlan` in front of the host path."""
 
     def __init__(self, emitter, files, windows=None, flips=None, _count=True):
         self.images = check_files(files)
         self.windows, self.flips, (h, w) = check_batch(self.images, windows, flips)
         # descriptors and layout are made where the batch is made (a generator's prefetch thread), not at upload time
         scans = [segment_scan(im) for im in self.images] if getattr(emitter, "device_entropy", False) else None
+        wider = None
+        if scans is not None and getattr(emitter, "unmarked", False) and not all(s.entropy_decodable for s in scans):
+            wider = [segment_scan(im, unmarked=True) for im in self.images]
+            if not (all(s.entropy_decodable for s in wider) and chunkable(wider, emitter.chunk_bytes)):
+                wider = None
         if scans is not None and all(s.entropy_decodable for s in scans):
             self.plan = EntropyCoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w), scans)
+        elif wider is not None:
+            self.plan = ChunkedEntropyCoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w), wider,
+                                                      emitter.chunk_bytes)
         else:
             self.plan = CoefficientPlan(self.images, self.windows, self.flips, blocks_for(h, w))
             if scans is not None and _count:
@@ -391,13 +481,20 @@ class DeviceCoefficientInputs(ds.StagingBuffers):
     here (two pinned buffers used in turn, the event behind the copy, the device blob grown on demand).  `n_threads`: host
     threads that entropy-decode a batch (None: `StagedPlan.fill`'s default).  `device_entropy`: batches whose files all carry
     restart intervals are entropy-decoded on the GPU (no host thread, the files' bytes are what goes up); `host_batches`
-    counts the batches that took the host path instead.  A segment that fails on the GPU cannot raise where the batch is
+    counts the batches that took the host path instead.  `unmarked` (needs `device_entropy`): batches with files that carry
+    no restart intervals are entropy-decoded on the GPU too, by chunks of `chunk_bytes` raw bytes (None:
+    DEFAULT_CHUNK_BYTES), when every file passes the wider pre-pass; only the rest counts as `host_batches`.  A segment that fails on the GPU cannot raise where the batch is
     emitted without a stall: its status reaches the host behind the batch, and the ValueError naming the file is raised
     when the staging slot is next used, or by `check`."""
 
-    def __init__(self, deconv=False, n_threads=None, device_entropy=False):
+    def __init__(self, deconv=False, n_threads=None, device_entropy=False, unmarked=False, chunk_bytes=None):
+        from .entropy_decode import check_chunk_bytes
+        if unmarked and not device_entropy:
+            raise ValueError("unmarked=True needs device_entropy=True: it widens what is entropy-decoded on the GPU")
         self.deconv = bool(deconv)
         self.device_entropy = bool(device_entropy)
+        self.unmarked = bool(unmarked)
+        self.chunk_bytes = check_chunk_bytes(DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes)
         self.host_batches = 0
         ds.StagingBuffers.__init__(self, n_threads)
 

@@ -89,6 +89,8 @@ def _lib():
         lib.dj_jpeg_scan_segments.restype = ctypes.c_int
         lib.dj_jpeg_scan_segments.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.POINTER(JpegSegmentInfo), ctypes.c_void_p,
                                               ctypes.c_long]
+        lib.dj_jpeg_scan_segments_unmarked.restype = ctypes.c_int
+        lib.dj_jpeg_scan_segments_unmarked.argtypes = lib.dj_jpeg_scan_segments.argtypes
         _LIB = lib
     return _LIB
 
@@ -115,21 +117,24 @@ def decode_info(buf):
     return inf
 
 
-def scan_segments(buf, max_segments=None):
+def scan_segments(buf, max_segments=None, unmarked=False):
     """The pre-pass of entropy decoding on the GPU (include/dj_jpeg_segments.h: dj_jpeg_scan_segments): headers and one
     search for 0xFF bytes, no Huffman decoding -> `SegmentScan`.  A file that is not eligible -- one the reader cannot
     parse included -- comes back with `entropy_decodable` False and a `reason`, never as an exception.  `max_segments`: an
-    upper bound the caller knows (the file's MCU count), which saves the first of two calls."""
+    upper bound the caller knows (the file's MCU count), which saves the first of two calls.  `unmarked=True`
+    (dj_jpeg_scan_segments_unmarked): a file without restart intervals is eligible too, as one segment that holds all its
+    MCUs (`restart_interval` = their number); every other file gives what it gives without."""
     buf = bytes(buf)
+    scan = _lib().dj_jpeg_scan_segments_unmarked if unmarked else _lib().dj_jpeg_scan_segments
     inf = JpegSegmentInfo()
     if len(buf) == 0:
         inf.reason = b"empty file"
         return SegmentScan(inf, _np.zeros((0, 2), dtype=_np.int64))
     ranges = _np.zeros((int(max_segments or 0), 2), dtype=_np.int64)
-    _check(_lib().dj_jpeg_scan_segments(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
+    _check(scan(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
     if inf.n_segments > len(ranges):
         ranges = _np.zeros((inf.n_segments, 2), dtype=_np.int64)
-        _check(_lib().dj_jpeg_scan_segments(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
+        _check(scan(buf, len(buf), ctypes.byref(inf), ranges.ctypes.data, len(ranges)))
     return SegmentScan(inf, ranges[:inf.n_segments].copy())
 
 

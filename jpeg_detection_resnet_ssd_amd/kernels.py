@@ -587,6 +587,41 @@ def jpeg_entropy_decode(data, desc_dev, desc_host, seg_dev, seg_host, tables_dev
     return out, status
 
 
+# ---- the same by chunks, for files without restart intervals: one lane per chunk ----------------------------------------------
+def jpeg_entropy_decode_chunked(data, desc_dev, desc_host, seg_dev, seg_host, tables_dev, tables_host, out, status, chunk_bytes,
+                                scratch, rounds=None, stream=None):
+    """dj_jpeg_entropy_decode_chunked: the arguments of `jpeg_entropy_decode` (the records' `reserved` holding each
+    segment's first chunk, as data/coefficient_inputs.py:`chunked_records` fills it), `chunk_bytes` (a multiple of 16 in
+    16..4096), `scratch` a 1-D uint8 CUDA tensor, 16-byte aligned, of at least the bytes the entry point asks for (it
+    refuses a shorter one), and optionally `rounds`, an int32 CUDA tensor that receives the synchronisation rounds of each
+    segment."""
+    import ctypes
+    import numpy as np
+    from ._lib import JpegEntropyDesc, JpegEntropySeg
+    from .data.coefficient_inputs import ENTROPY_DTYPE, SEGMENT_DTYPE
+    from .jpeg2dct.numpy import HUFF_BYTES
+    n = _check_staged(desc_host, ENTROPY_DTYPE, JpegEntropyDesc, desc_dev,
+                      ((data, "data"), (desc_dev, "desc_dev"), (seg_dev, "seg_dev"), (tables_dev, "tables_dev"), (out, "out"),
+                       (scratch, "scratch")))
+    assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(JpegEntropySeg), "segment-record layouts disagree"
+    assert isinstance(seg_host, np.ndarray) and seg_host.dtype == SEGMENT_DTYPE and seg_host.ndim == 1 \
+        and seg_host.flags.c_contiguous, "seg_host: expected a contiguous 1-D array of SEGMENT_DTYPE"
+    assert seg_dev.numel() >= seg_host.nbytes and seg_dev.data_ptr() % 8 == 0, "seg_dev: too small or misaligned"
+    assert isinstance(tables_host, np.ndarray) and tables_host.dtype == np.uint8 and tables_host.ndim == 2 \
+        and tables_host.shape[1] == HUFF_BYTES, "tables_host: expected an (n_tables, %d) uint8 array" % HUFF_BYTES
+    assert tables_dev.numel() >= tables_host.size, "tables_dev: smaller than the tables"
+    for t, name in ((status, "status"),) + (((rounds, "rounds"),) if rounds is not None else ()):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() \
+            and t.numel() >= seg_host.shape[0], "%s: expected a contiguous int32 CUDA tensor of one entry per segment" % name
+    check(_L().dj_jpeg_entropy_decode_chunked(ptr(data), data.numel(), ptr(desc_dev), desc_host.ctypes.data, n, ptr(seg_dev),
+                                              seg_host.ctypes.data, seg_host.shape[0], ptr(tables_dev), tables_host.shape[0],
+                                              ptr(out), out.numel(), ptr(status), int(chunk_bytes), ptr(scratch), scratch.numel(),
+                                              ptr(rounds) if rounds is not None else None,
+                                              stream if stream is not None else _stream()),
+          "dj_jpeg_entropy_decode_chunked")
+    return out, status
+
+
 # ---- Pascal-VOC evaluation: greedy matching, then cumulative counts / precision / recall / sampled AP -------------------------
 def _check_eval_tensor(t, name, dtype, numel):
     assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel, \

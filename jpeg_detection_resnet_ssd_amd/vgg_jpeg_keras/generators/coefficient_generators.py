@@ -14,7 +14,9 @@ ValueError naming its path: files are expected to be pre-sized (tools/presize_da
 window, mirror and de-quantisation on the GPU when the model uploads the batch.  `device_entropy=True` on top of it: a
 batch whose files all carry restart intervals (tools/presize_dataset.py --restart-rows / --restart-mcus) is entropy-decoded
 on the GPU too, from the files' bytes, with no host thread; any other batch takes the host threads (`host_batches` counts
-them).  `device=False` returns the host statement's
+them).  `unmarked=True` on top of that: batches with ordinary files, which carry no restart intervals, are entropy-decoded on
+the GPU as well, by chunks (`chunk_bytes`); only a batch with a file that even the wider pre-pass refuses takes the host
+threads.  `device=False` returns the host statement's
 arrays.  Both make the same draws and leave `random` in the same state."""
 import os
 import random
@@ -31,11 +33,13 @@ class DCTGeneratorCoefficients(Sequence):
     deconv = False
 
     def __init__(self, data_directory, index_file, batch_size=32, shuffle=True, target_length=224, random_crop=True,
-                 flip=True, device=True, decode_threads=None, device_entropy=False):
+                 flip=True, device=True, decode_threads=None, device_entropy=False, unmarked=False, chunk_bytes=None):
         if int(target_length) < MCU or int(target_length) % MCU:
             raise ValueError("target_length must be a positive multiple of %d, got %r" % (MCU, target_length))
         if device_entropy and not device:
             raise ValueError("device_entropy needs device=True: the files are entropy-decoded where the batch is uploaded")
+        if unmarked and not device_entropy:
+            raise ValueError("unmarked needs device_entropy=True: it widens what is entropy-decoded on the GPU")
         self.association, self.classes, self.images_path = prepare_imagenet(index_file, data_directory)
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -48,7 +52,8 @@ class DCTGeneratorCoefficients(Sequence):
         self.batches_per_epoch = len(self.images_path) // self.batch_size
         self.indexes = np.arange(len(self.images_path))
         self._emit = DeviceCoefficientInputs(deconv=self.deconv, n_threads=decode_threads,
-                                             device_entropy=device_entropy) if device else None
+                                             device_entropy=device_entropy, unmarked=unmarked,
+                                             chunk_bytes=chunk_bytes) if device else None
         self.on_epoch_end()
 
     def __len__(self):
@@ -84,7 +89,8 @@ class DCTGeneratorCoefficients(Sequence):
 
     @property
     def host_batches(self):
-        """Batches that `device_entropy=True` could not take because a file had no restart intervals."""
+        """Batches that `device_entropy=True` could not take because a file had no restart intervals (with
+        `unmarked=True`: because a file failed the wider pre-pass too)."""
         return self._emit.host_batches if self._emit is not None else 0
 
     def _draws(self, path, height, width):

@@ -82,6 +82,15 @@ def device_entropy_switch(environ=os.environ):
     return coefficient_switch(environ) and environ.get("DJ_DEVICE_ENTROPY", "0") == "1"
 
 
+def unmarked_switch(environ=os.environ):
+    """Whether the coefficient generators entropy-decode files WITHOUT restart intervals on the GPU as well, by chunks:
+    `DJ_DEVICE_ENTROPY_UNMARKED=1`, which needs `DJ_DEVICE_ENTROPY=1` (ValueError without it)."""
+    on = environ.get("DJ_DEVICE_ENTROPY_UNMARKED", "0") == "1"
+    if on and not device_entropy_switch(environ):
+        raise ValueError("DJ_DEVICE_ENTROPY_UNMARKED=1 needs DJ_DEVICE_ENTROPY=1: it widens what that switch decodes on the GPU")
+    return on
+
+
 class DCTGeneratorJPEG2DCT(Sequence):
     """Batches of `[X_y, X_cbcr]` ((B, T/8, T/8, 64), (B, T/16, T/16, 128)) and one-hot labels."""
     deconv = False

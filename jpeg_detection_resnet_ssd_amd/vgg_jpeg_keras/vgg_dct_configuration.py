@@ -138,11 +138,11 @@ class VGGDCTTrainingConfiguration(object):
     def _coefficient_generator(self, directory, index_file, training):
         """`DJ_COEFFICIENT_INPUTS=1`: pre-sized files fed as their own coefficients -- a random window and mirror for
         training, the centred window and no mirror for validation and test."""
-        from .generators import DCTGeneratorCoefficients, device_entropy_switch
+        from .generators import DCTGeneratorCoefficients, device_entropy_switch, unmarked_switch
         return DCTGeneratorCoefficients(directory, index_file, self._batch_size, target_length=self.img_size[0],
                                         random_crop=training, flip=training,
                                         decode_threads=int(environ.get("DJ_DECODE_THREADS", "16")),
-                                        device_entropy=device_entropy_switch())
+                                        device_entropy=device_entropy_switch(), unmarked=unmarked_switch())
 
     def prepare_training_generators(self):
         rank = self.horovod.rank() if self.horovod is not None else 0

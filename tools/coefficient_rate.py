@@ -17,6 +17,10 @@
       yardstick; (d)'s outputs are asserted equal to (c)'s.  `emit_into`, fill, bytes uploaded, the entropy kernel by
       events and over 50 launches back to back, and what the markers add to the files; then all of it again for
       `restart_marker_blocks=4` (four times the segments, more marker bytes)
+  (e) the ordinary files of (c), which carry no restart intervals, entropy-decoded on the GPU by chunks:
+      DCTGeneratorCoefficients(device=True, device_entropy=True, unmarked=True, chunk_bytes=...) for chunks of 64, 128, 256
+      and 512 bytes -- `emit_into`, bytes uploaded, dj_jpeg_entropy_decode_chunked by events over 50 launches back to
+      back, the median synchronisation rounds per file -- beside (c) of the same run, the yardstick; outputs asserted equal
 
     python tools/coefficient_rate.py [--reps 20]
 
@@ -155,6 +159,54 @@ def entropy_rows(res, key, root, plain_bytes, bufs, reps, dev, **restart):
     assert not plan.status_view(scratch).any().item()
 
 
+CHUNK_SIZES = (64, 128, 256, 512)
+
+
+def unmarked_rows(res, directory, index_file, bufs, reps, dev):
+    """Row (e): the plain files through the chunked plan at every chunk size of CHUNK_SIZES; (c) was measured on them."""
+    from jpeg_detection_resnet_ssd_amd.data.coefficient_inputs import ChunkedEntropyCoefficientPlan
+    from jpeg_detection_resnet_ssd_amd.vgg_jpeg_keras.generators import DCTGeneratorCoefficients
+    want = None
+    for chunk_bytes in CHUNK_SIZES:
+        key = "e%d" % chunk_bytes
+        gen = DCTGeneratorCoefficients(directory, index_file, batch_size=B, shuffle=False, target_length=T, device=True,
+                                       decode_threads=THREADS, device_entropy=True, unmarked=True, chunk_bytes=chunk_bytes)
+        pending = generator_rows(res, key, gen, bufs, reps)
+        gen.check_inputs()
+        plan = pending.plan
+        assert gen.host_batches == 0 and type(plan) is ChunkedEntropyCoefficientPlan, "every batch must take the chunked plan"
+        if want is None:
+            host_pending = DCTGeneratorCoefficients(directory, index_file, batch_size=B, shuffle=False, target_length=T,
+                                                    device=True, decode_threads=THREADS)
+            random.seed(1)
+            want = [torch.empty_like(b) for b in bufs]
+            host_pending[0][0].emit_into(want)
+            torch.cuda.synchronize()
+        res[key + "_equals_c"] = all(bool((b == w).all()) for b, w in zip(bufs, want))
+        assert res[key + "_equals_c"], "the chunked plan and the host reader disagree"
+        res[key + "_chunks"] = plan.n_chunks
+        staging, blob = staged(plan, pending.images, dev)
+        host = staging.numpy()
+        res[key + "_fill_ms"] = median_ms(lambda: plan.fill(host, pending.images), reps)
+        res[key + "_upload_ms"] = median_ms(lambda: blob.copy_(staging, non_blocking=True), reps)
+        scratch = torch.empty(plan.scratch_bytes, dtype=torch.uint8, device=dev)
+        rounds = torch.zeros(plan.n_status, dtype=torch.int32, device=dev)
+        edesc_h, segs_h, huff_h, _ = plan.entropy_views(host)
+        edesc_d, segs_d, huff_d, bytes_d = plan.entropy_views(blob)
+
+        def entropy():
+            kernels.jpeg_entropy_decode_chunked(bytes_d, edesc_d, edesc_h, segs_d, segs_h, huff_d, huff_h, scratch[:plan.coef_bytes],
+                                                plan.status_view(scratch), chunk_bytes,
+                                                scratch[plan.work_offset:plan.work_offset + plan.work_bytes], rounds=rounds)
+        res[key + "_entropy_kernel_ms"] = event_ms(entropy, max(50, reps))
+        res[key + "_entropy_kernel_50_back_to_back_ms"] = event_ms(entropy, reps, launches=50)
+        res[key + "_both_kernels_ms"] = event_ms(lambda: plan.launch(host, blob, bufs, scratch), max(50, reps))
+        torch.cuda.synchronize()
+        assert not plan.status_view(scratch).any().item()
+        per_file = rounds.cpu().numpy()
+        res[key + "_rounds_median"], res[key + "_rounds_max"] = float(np.median(per_file)), int(per_file.max())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -221,6 +273,9 @@ def main():
         entropy_rows(res, "rows1", root, plain_bytes, bufs, reps, dev, restart_marker_rows=1)
         entropy_rows(res, "mcus4", root, plain_bytes, bufs, reps, dev, restart_marker_blocks=4)
 
+        # (e) the plain files by chunks
+        unmarked_rows(res, directory, index_file, bufs, reps, dev)
+
     def cell(v):
         return "%.2f (%.2f - %.2f)" % tuple(v) if isinstance(v, tuple) else ("%.2f" % v if isinstance(v, float) else str(v))
     rows = [("files on disk to input tensors: `gen[0]` + `emit_into` (ms)", "a_batch_and_emit_ms", None, "c_batch_and_emit_ms"),
@@ -250,6 +305,21 @@ def main():
                         ("dj_jpeg_entropy_decode, 50 launches back to back (ms each)", "_d_entropy_kernel_50_back_to_back_ms"),
                         ("both kernels by events (ms)", "_d_both_kernels_ms")):
             print("| %s | - | - | %s |" % (name, cell(res[key + k])))
+    print()
+    print("| files without restart intervals (%.2f MB) | (c) 16 host threads | %s |"
+          % (res["files_MB"], " | ".join("(e) chunks of %d" % n for n in CHUNK_SIZES)))
+    print("|---|---|%s" % ("---|" * len(CHUNK_SIZES)))
+    for name, c, suffix in (("`gen[0]` + `emit_into` (ms)", "c_batch_and_emit_ms", "_batch_and_emit_ms"),
+                            ("`emit_into` (ms)", "c_emit_only_ms", "_emit_only_ms"), ("fill (ms)", "c_fill_ms", "_fill_ms"),
+                            ("bytes uploaded (MB)", "c_blob_MB", "_blob_MB"), ("upload from pinned memory (ms)", "c_upload_ms", "_upload_ms"),
+                            ("chunks", None, "_chunks"), ("synchronisation rounds per file, median", None, "_rounds_median"),
+                            ("synchronisation rounds per file, most", None, "_rounds_max"),
+                            ("dj_jpeg_entropy_decode_chunked by events (ms)", None, "_entropy_kernel_ms"),
+                            ("dj_jpeg_entropy_decode_chunked, 50 launches back to back (ms each)", None,
+                             "_entropy_kernel_50_back_to_back_ms"),
+                            ("both kernels by events (ms)", "c_kernel_ms", "_both_kernels_ms")):
+        print("| %s | %s | %s |" % (name, "-" if c is None else cell(res[c]),
+                                    " | ".join(cell(res["e%d%s" % (n, suffix)]) for n in CHUNK_SIZES)))
     print(json.dumps(res), flush=True)
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""Pascal-VOC mAP evaluation of a trained SSD300 ResNet50-DCT model on MI355X: the entry point of
-localisation_part/evaluation.py (same positional `weights`, `--archi`, dataset flags; `-r/--ssd_resnet` is the only
-model family built here), `mode='inference'` model with the on-device DecodeDetections layer, `Evaluator(...)` with the
+"""Pascal-VOC mAP evaluation of a trained SSD300 ResNet50-DCT or VGG-DCT model on MI355X: the entry point of
+localisation_part/evaluation.py (same positional `weights`, `--archi`, dataset flags; `-r/--ssd_resnet`, which is also the
+default, selects the ResNet50-DCT family by `--archi`, `-sd/--ssd_dct` the VGG-DCT `ssd_300DCT` whatever `--archi` says; the
+other VGG switches are refused), `mode='inference'` model with the on-device DecodeDetections layer, `Evaluator(...)` with the
 reference's settings (evaluation.py:102-131: batch 8, 'resize', 11-point sampling, IoU 0.5, 'include' borders).
 Matching, precision / recall and AP run on the GPU (csrc/dj_eval.hip, results equal bit for bit to the host loop, equal
 confidences ranked in list order), and the detections stay on the GPU from the DecodeDetections layer to the matching
@@ -36,8 +37,9 @@ parser.add_argument("--host_matching", action="store_true", default=False,
 parser.add_argument("--host_predictions", action="store_true", default=False,
                     help="download every decoded batch and collect the detections in python lists instead of on the GPU")
 args = parser.parse_args()
-if args.ssd or args.ssd_other or args.ssd_dct or args.ssd_miisst or args.ssd_miisst_dct:
-    raise SystemExit("only the ResNet50-DCT SSD family (-r, --archi ...) is built here; the VGG models are out of scope")
+if args.ssd or args.ssd_other or args.ssd_miisst or args.ssd_miisst_dct:
+    raise SystemExit("only the ResNet50-DCT SSD family (-r, --archi ...) and the VGG-DCT SSD300 (-sd) are built here; the "
+                     "other VGG models are out of scope")
 
 from jpeg_detection_resnet_ssd_amd.eval_utils.average_precision_evaluator import Evaluator  # noqa: E402
 from jpeg_detection_resnet_ssd_amd.keras import backend as K  # noqa: E402
@@ -56,7 +58,14 @@ ssd_params = {"image_size": (img_height, img_width, 3), "n_classes": n_classes, 
               "variances": [0.1, 0.1, 0.2, 0.2], "normalize_coords": True, "subtract_mean": [123, 117, 104],
               "swap_channels": [2, 1, 0], "confidence_thresh": 0.01, "iou_threshold": 0.45, "top_k": 200,
               "nms_max_output_size": 400, "archi": args.archi}
-model = (ssd_resnet_EF_layers_custom if args.archi == "ssd_custom" else ssd_resnet_EF_layers_identical)(**ssd_params)
+if args.ssd_dct:
+    # the VGG-DCT SSD300 (the reference builds its no_reg twin here: the same inference graph); it has no `archi`
+    from jpeg_detection_resnet_ssd_amd.models.keras_ssd300_dct_j2d import ssd_300DCT
+    args.archi = None
+    del ssd_params["archi"]
+    model = ssd_300DCT(**ssd_params)
+else:
+    model = (ssd_resnet_EF_layers_custom if args.archi == "ssd_custom" else ssd_resnet_EF_layers_identical)(**ssd_params)
 if args.weights != "random":
     model.load_weights(args.weights)
 model.compile(optimizer=SGD(lr=0.001, momentum=0.9, decay=0.0, nesterov=False),

@@ -66,19 +66,24 @@ def _check_ssd_arguments(n_predictor_layers, min_scale, max_scale, scales, aspec
     return scales, aspect_ratios, n_boxes, steps, offsets, variances
 
 
-def _head_conv(x, filters, kernel, name, l2_reg, strides=(1, 1), padding="same", dilation=(1, 1)):
+def _kernel_args(l2_reg, regularized=True):
+    """he_normal and an l2 kernel regulariser; with `regularized=False`, which only the `*_no_reg` VGG builder passes,
+    Keras' own defaults (glorot_uniform, no regulariser)."""
+    return {"kernel_initializer": "he_normal", "kernel_regularizer": l2(l2_reg)} if regularized else {}
+
+
+def _head_conv(x, filters, kernel, name, l2_reg, strides=(1, 1), padding="same", dilation=(1, 1), regularized=True):
     """SSD extra-feature conv: fused ReLU, he_normal, l2 kernel regulariser, no BatchNormalization."""
     return Conv2D(filters, kernel, strides=strides, dilation_rate=dilation, activation="relu", padding=padding,
-                  kernel_initializer="he_normal", kernel_regularizer=l2(l2_reg), name=name)(x)
+                  name=name, **_kernel_args(l2_reg, regularized))(x)
 
 
 def _multibox(sources, model_inputs, n_classes, n_boxes, l2_reg, img_height, img_width, scales, aspect_ratios,
               two_boxes_for_ar1, steps, offsets, clip_boxes, variances, coords, normalize_coords, mode,
-              return_predictor_sizes, decode_args):
+              return_predictor_sizes, decode_args, regularized=True):
     """Predictor convs, anchors, reshape/concat/softmax assembly (keras_ssd300_dct_j2d_resnet.py:562-932)."""
     def predictor(x, ch, name):
-        return Conv2D(ch, (3, 3), padding="same", kernel_initializer="he_normal", kernel_regularizer=l2(l2_reg),
-                      name=name)(x)
+        return Conv2D(ch, (3, 3), padding="same", name=name, **_kernel_args(l2_reg, regularized))(x)
 
     conf = [predictor(s, n_boxes[i] * n_classes, "{}_mbox_conf_{}".format(_SOURCE_NAMES[i], n_classes))
             for i, s in enumerate(sources)]

@@ -4,7 +4,8 @@ SGD(0.001, 0.9), SSDLoss(3, 1.0), synthetic JPEG-DCT inputs and encoder-made tar
 import numpy as np
 
 # algorithmic conv+deconv work, forward+dgrad+wgrad (BASELINE.md section 2 / SURVEY 8(d))
-TRAIN_GFLOP_PER_IMAGE = {"ssd_custom": 41.60, "deconv": 74.43, "up_sampling": 74.36}
+# ssd_300DCT: 15.055 GMAC forward per image (29 convolutions, sum of OH*OW*KH*KW*Cin*Cout) x 2 FLOP x 3 passes
+TRAIN_GFLOP_PER_IMAGE = {"ssd_custom": 41.60, "deconv": 74.43, "up_sampling": 74.36, "ssd_300DCT": 90.33}
 
 SSD_ARGS = dict(image_size=(300, 300, 3), n_classes=20, mode="training", l2_regularization=0.0005,
                 scales=[0.1, 0.2, 0.37, 0.54, 0.71, 0.88, 1.05],
@@ -22,8 +23,12 @@ def build_ssd(archi, weight_seed=42, compile_model=True):
     from .models.keras_ssd300_dct_j2d_resnet import ssd_resnet_EF_layers_custom, ssd_resnet_EF_layers_identical
     K.clear_session()
     K.set_random_seed(weight_seed)
-    fn = ssd_resnet_EF_layers_custom if archi == "ssd_custom" else ssd_resnet_EF_layers_identical
-    model, sizes = fn(archi=archi, return_predictor_sizes=True, **SSD_ARGS)
+    if archi == "ssd_300DCT":     # the VGG-DCT detector (models/keras_ssd300_dct_j2d.py): no `archi` argument
+        from .models.keras_ssd300_dct_j2d import ssd_300DCT
+        model, sizes = ssd_300DCT(return_predictor_sizes=True, **SSD_ARGS)
+    else:
+        fn = ssd_resnet_EF_layers_custom if archi == "ssd_custom" else ssd_resnet_EF_layers_identical
+        model, sizes = fn(archi=archi, return_predictor_sizes=True, **SSD_ARGS)
     if compile_model:
         model.compile(optimizer=SGD(lr=0.001, momentum=0.9, decay=0.0, nesterov=False),
                       loss=SSDLoss(neg_pos_ratio=3, alpha=1.0).compute_loss)

@@ -470,7 +470,11 @@ POOL_GEOMS = [
     PoolCase("3x3s2same6x7", 6, 7, 3, 3, 2, 2, 0, 1, 3, 4),       # TF 'same' of an even and an odd extent: pt 0, pl 1
     PoolCase("2x2s2valid", 5, 7, 2, 2, 2, 2, 0, 0, 2, 3),
     PoolCase("2x2s3gaps", 5, 7, 2, 2, 3, 3, 0, 0, 2, 2),          # rows 2 and columns 2, 5, 6 belong to no window
+    # windows and strides that differ between the axes: an H/W swap of either changes the output shape
+    PoolCase("2x3s1x2", 5, 7, 2, 3, 1, 2, 0, 0, 4, 3),
+    PoolCase("3x2s2x1same", 6, 7, 3, 2, 2, 1, 0, 0, 3, 7),        # TF 'same': one trailing pad row and column, none in front
 ]
+POOL_ANISOTROPIC = ("2x3s1x2", "3x2s2x1same")
 POOL_C = [4, 6]
 POOL_DATA = ["mixed", "negative", "relu"]
 POOL_ARGMAX = [None, 0, 1]      # no saved arg-max, saved at byte offset 0, saved at byte offset 1

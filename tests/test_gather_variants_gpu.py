@@ -5,7 +5,8 @@ per-tap row offsets cached across the K-steps of a tap (NP 2: forward, input gra
 every K-step.  A twin pair sums the same products in the same order, so every comparison is torch.equal;
 `dj_set_gather_variants` picks the twin of either family inside one process.
 
-Geometries: the smallest at which each carry and edge of the walk / each tap edge occurs (see GEOMS).  The prologue's
+Geometries: the smallest at which each carry and edge of the walk / each tap edge occurs, and three whose kernel, strides or
+dilation differ between the axes (see GEOMS).  The prologue's
 shift is larger in magnitude than the data, so a padding pixel that is not zeroed AFTER the prologue shows.
 
 Split-K in the bit-equality test: the forward pass goes through slabs + the fixed-order reduction; the gradients have
@@ -25,7 +26,7 @@ TOL = {"float32x3": 3e-5, "float32x6": 2e-6}   # rel-L2 per GEMM: the bounds of 
 TOL["float32_mfma"] = TOL["float32x6"]
 MODES = ["float32x6", "float32x3", "float32_mfma"]
 
-# (batch, H, W, Cin, Cout, k, stride, padding, dilation)
+# (batch, H, W, Cin, Cout, k, stride, padding, dilation); k, stride and dilation: one int for both axes, or an (h, w) pair
 GEOMS = [
     (2, 7, 5, 128, 96, 3, 1, "same", 1),      # non-square map, a row shorter than a K-step
     (3, 3, 3, 128, 64, 3, 1, "same", 1),      # a map smaller than a K-step: an image carry every step
@@ -35,7 +36,16 @@ GEOMS = [
     (2, 6, 6, 128, 64, 3, 1, "valid", 1),
     (2, 8, 8, 256, 64, 1, 2, "valid", 1),     # strided 1x1: the weight gradient walks
     (2, 6, 6, 192, 64, 3, 1, "same", 1),      # Cin % 128 != 0: the 128-row tiles fall back to the plain kernel
+    # geometries that differ between the axes (tests/conv_geometry_cases.py): the tap cache's (kh, kw) wrap at KW != KH, the
+    # walk's carries at sH != sW, the tap offsets at dH != dW and pads 1 / 3
+    (2, 9, 12, 128, 64, (2, 3), 1, "same", 1),
+    (2, 11, 9, 128, 64, 3, (2, 1), "same", 1),     # (an output row of 9 pixels: every K-step of the walk carries)
+    (1, 12, 9, 128, 64, 3, 1, "same", (1, 3)),
 ]
+
+
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
 
 
 @pytest.fixture()
@@ -57,21 +67,22 @@ def case(geom):
     from jpeg_detection_resnet_ssd_amd import kernels as Kn
     from oracle import keras_ops as ko
     b, h, w, ci, co, k, s, pad, dil = geom
+    k, s, dil = _pair(k), _pair(s), _pair(dil)
     g = torch.Generator().manual_seed(11)
     x = torch.randn(b, h, w, ci, generator=g)
-    wt = torch.randn(k, k, ci, co, generator=g) * (2.0 / (k * k * ci)) ** 0.5
+    wt = torch.randn(k[0], k[1], ci, co, generator=g) * (2.0 / (k[0] * k[1] * ci)) ** 0.5
     sc = torch.rand(ci, generator=g) + 0.5
     # |shift| in [8, 9): above |x * scale| (< 1.5 * 5.5), both signs -- a padding pixel left at `shift` would be seen
     sh = (8.0 + torch.rand(ci, generator=g)) * torch.where(torch.rand(ci, generator=g) < 0.75, 1.0, -1.0)
     xa = torch.relu(x * sc + sh)
     xr, wr = xa.double().requires_grad_(True), wt.double().requires_grad_(True)
-    yr = ko.conv2d(xr, wr, None, (s, s), pad, (dil, dil))
+    yr = ko.conv2d(xr, wr, None, s, pad, dil)
     dy = torch.randn(*yr.shape, generator=g) * 1e-3
     yr.backward(dy.double())
     w_plain, x_plain = wt.double().requires_grad_(True), x.double().requires_grad_(True)
-    y_plain = ko.conv2d(x_plain, w_plain, None, (s, s), pad, (dil, dil))
+    y_plain = ko.conv2d(x_plain, w_plain, None, s, pad, dil)
     y_plain.backward(dy.double())
-    desc = Kn.make_conv_desc(b, h, w, ci, co, (k, k), (s, s), pad, (dil, dil))
+    desc = Kn.make_conv_desc(b, h, w, ci, co, k, s, pad, dil)
     dev = {n: t.cuda() for n, t in (("x", x), ("w", wt), ("dy", dy), ("sc", sc), ("sh", sh))}
     ref = {"y_pro": yr.detach(), "y": y_plain.detach(), "dx": x_plain.grad, "dw_pro": wr.grad, "dw": w_plain.grad}
     return desc, dev, ref

@@ -165,6 +165,25 @@ def test_pool_ties_and_gaps():
     assert not (code0 == 255).any() and np.array_equal(y, y0)
 
 
+def test_anisotropic_pool_cases_hold_what_the_library_computes():
+    """The two cases whose window and strides differ between the axes: pads and output size as conv_geometry resolves
+    them, every pixel covered, and an H/W swap of the window or of the strides changes the output size or the pads."""
+    from jpeg_detection_resnet_ssd_amd.kernels import conv_geometry
+    by_name = {g.name: g for g in nc.POOL_GEOMS}
+    assert set(nc.POOL_ANISOTROPIC) <= set(by_name)
+    for name, padding in (("2x3s1x2", "valid"), ("3x2s2x1same", "same")):
+        g = by_name[name]
+        assert g.kh != g.kw and g.sh != g.sw
+        assert conv_geometry(g.H, g.W, (g.kh, g.kw), (g.sh, g.sw), padding, (1, 1)) == (g.pt, g.pl, g.OH, g.OW)
+        for kernel, strides in (((g.kw, g.kh), (g.sh, g.sw)), ((g.kh, g.kw), (g.sw, g.sh))):
+            swapped = conv_geometry(g.H, g.W, kernel, strides, padding, (1, 1))
+            assert swapped != (g.pt, g.pl, g.OH, g.OW)                     # ('same' keeps the size: the pads move)
+            assert swapped[2:] != (g.OH, g.OW) or (padding == "same" and strides == (g.sh, g.sw))
+    assert not nc.pool_uncovered(by_name["3x2s2x1same"]).any()
+    unc = nc.pool_uncovered(by_name["2x3s1x2"])      # rows: windows at 0..3 of height 2 reach row 4; columns 0..6 all
+    assert not unc.any()
+
+
 def test_pool_paths():
     assert nc.pool4(4, 4, 4, None) and nc.pool4(4, 4, 4, 0) and not nc.pool4(4, 4, 4, 1) and not nc.pool4(6, 4, 4, 0)
     assert [nc.pool_bwd_path(4, 4, 4, a) for a in nc.POOL_ARGMAX] == ["bwd_rescan", "bwd4", "bwd_saved_scalar"]

@@ -399,7 +399,18 @@ int dj_categorical_crossentropy(const float* y_true, const float* probs, long ro
  *                      p = p - lr * u;   d = rho * d + one_minus_rho * (u * u)
  *   with lr = lr / (1 + decay * iterations) and one_minus_rho = (float)(1.0 - rho), subtracted in double as Keras does with
  *   its Python float, both computed by the caller.
- * All three.  sumsq != NULL: sumsq[0] += sum(p^2) before the update, in one fp32 addition.  One thread per four
+ * RMSprop, Adagrad, Adamax and Nadam (Keras 2.2.4 get_updates; rmsprop_host, adagrad_host, adamax_host, nadam_host) on
+ * the same g'; lr below is lr / (1 + decay * iterations), t = iterations + 1, 1 - rho and 1 - beta are subtracted in fp32:
+ * dj_rmsprop_update:   a = rho * a + (1 - rho) * (g' * g');   p = p - (lr * g') / (sqrt(a) + epsilon)
+ * dj_adagrad_update:   a = a + g' * g';                       p = p - (lr * g') / (sqrt(a) + epsilon)
+ * dj_adamax_update:    m = beta_1 * m + (1 - beta_1) * g';    u = max(beta_2 * u, |g'|), a NaN on either side giving NaN
+ *                      p = p - (lr_t * m) / (u + epsilon)     with lr_t = lr / (1 - beta_1^t) (Adamax.step_size())
+ * dj_nadam_update:     m and v as Adam's;   mbar = one_minus_mc_t * (g' * c_g) + mc_t1 * (m * c_m)
+ *                      p = p - (lr * mbar) / (sqrt(v * c_v) + epsilon)
+ *   with mc(i) = beta_1 * (1 - 0.5 * 0.96^(i * schedule_decay)), S = mc(1) * ... * mc(t), c_g = 1 / (1 - S),
+ *   c_m = 1 / (1 - S * mc(t + 1)), c_v = 1 / (1 - beta_2^t), one_minus_mc_t = 1 - mc(t), mc_t1 = mc(t + 1), computed in
+ *   double by the caller (Nadam.step_scalars()): products with reciprocals where Keras divides.
+ * All of them.  sumsq != NULL: sumsq[0] += sum(p^2) before the update, in one fp32 addition.  One thread per four
  * consecutive elements in a grid-stride loop of at most dj_optim_groups_per_pass() threads; 16-byte accesses when every
  * pointer is 16-byte aligned, element by element otherwise.  DJ_ERR_ARG for a null pointer (vhat and sumsq excepted),
  * n <= 0, or buffers that overlap. ---- */
@@ -412,6 +423,15 @@ int dj_adam_update(float* param, const float* grad, float* m, float* v, float* v
 int dj_adadelta_update(float* param, const float* grad, float* accum, float* delta_accum, long n, float lr, float rho,
                        float one_minus_rho, float epsilon, float l2, float grad_scale, float* sumsq /* may be NULL */,
                        void* stream);
+int dj_rmsprop_update(float* param, const float* grad, float* accum, long n, float lr, float rho, float epsilon, float l2,
+                      float grad_scale, float* sumsq /* may be NULL */, void* stream);
+int dj_adagrad_update(float* param, const float* grad, float* accum, long n, float lr, float epsilon, float l2,
+                      float grad_scale, float* sumsq /* may be NULL */, void* stream);
+int dj_adamax_update(float* param, const float* grad, float* m, float* u, long n, float lr_t, float beta_1, float beta_2,
+                     float epsilon, float l2, float grad_scale, float* sumsq /* may be NULL */, void* stream);
+int dj_nadam_update(float* param, const float* grad, float* m, float* v, long n, float lr, float beta_1, float beta_2,
+                    float epsilon, float c_g, float c_m, float c_v, float one_minus_mc_t, float mc_t1, float l2,
+                    float grad_scale, float* sumsq /* may be NULL */, void* stream);
 
 /* ---- DecodeDetections (L/keras_layers/keras_layer_DecodeDetections.py:109-265; numpy twin
  * L/ssd_encoder_decoder/ssd_output_decoder.py:111-226): y_pred [batch][n_boxes][n_classes+12] (centroid offsets, anchors,

@@ -192,6 +192,10 @@ SIGNATURES = {
                                c_void_p]),
     "dj_adadelta_update": (c_int, [FP, FP, FP, FP, c_long, c_float, c_float, c_float, c_float, c_float, c_float, FP,
                                    c_void_p]),
+    "dj_rmsprop_update": (c_int, [FP, FP, FP, c_long] + [c_float] * 5 + [FP, c_void_p]),
+    "dj_adagrad_update": (c_int, [FP, FP, FP, c_long] + [c_float] * 4 + [FP, c_void_p]),
+    "dj_adamax_update": (c_int, [FP, FP, FP, FP, c_long] + [c_float] * 6 + [FP, c_void_p]),
+    "dj_nadam_update": (c_int, [FP, FP, FP, FP, c_long] + [c_float] * 11 + [FP, c_void_p]),
     "dj_decode_detections_workspace_floats": (c_long, [c_int, c_int, c_int, c_int]),
     "dj_decode_detections": (c_int, [FP, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, c_int, FP, FP,
                                      c_void_p]),

@@ -1,5 +1,6 @@
-// keras.optimizers.SGD, Adam (with amsgrad) and Adadelta: one memory-bound pass over a segment of the flat parameter
-// buffer, equal bit for bit to sgd_host / adam_host / adadelta_host of keras/optimizers.py (the host statement).  All
+// keras.optimizers.SGD, Adam (with amsgrad), Adadelta, RMSprop, Adagrad, Adamax and Nadam: one memory-bound pass over a
+// segment of the flat parameter buffer, equal bit for bit to sgd_host / adam_host / adadelta_host / rmsprop_host /
+// adagrad_host / adamax_host / nadam_host of keras/optimizers.py (the host statement).  All
 // arithmetic is fp32, every product, sum, quotient and square root rounded once in the order the statement writes them:
 // nothing is contracted into an fma, hence the pragma, and the fmas of the SGD statement are written out as
 // __builtin_fmaf; the division and sqrtf are hipcc's correctly rounded expansions.
@@ -11,7 +12,7 @@
 // is read once and written once per step and a segment of a real model is far larger than the L2, so the gradient and the
 // state buffers move with non-temporal loads and stores; the parameters, which the next forward pass reads, keep the
 // default policy.  sumsq != NULL: sum(p^2) of the pre-update parameters goes through dj_sumsq_finish; the slots are
-// shared by the three rules.
+// shared by all rules.
 //
 // SGD used to be a kernel of its own in dj_loss.hip (one element per thread, 4096 workgroups, default cache policy, null
 // checks only).  As a rule of this file it gained the four-per-thread geometry, so that dj_optim_groups_per_pass()
@@ -113,6 +114,74 @@ struct DjAdadeltaRule {
     const float u = (ge * sqrtf(s[1] + eps)) / sqrtf(s[0] + eps);
     p = p - lr * u;
     s[1] = rho * s[1] + omr * (u * u);
+  }
+};
+
+// a = rho*a + (1 - rho)*g'^2 ; p = p - (lr*g') / (sqrt(a) + eps)
+struct DjRmspropRule {
+  static constexpr int NS = 1;
+  static constexpr const char* NAME = "dj_rmsprop_update";
+  static constexpr const char* BUFFERS = "param, grad and accum";
+  static constexpr const char* STATE[NS] = {"accum"};
+  float* state[NS];
+  float lr, rho, omr, eps, l2x2, grad_scale;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * grad_scale + l2x2 * p;
+    s[0] = rho * s[0] + omr * (ge * ge);
+    p = p - (lr * ge) / (sqrtf(s[0]) + eps);
+  }
+};
+
+// a = a + g'^2 ; p as RMSprop's
+struct DjAdagradRule {
+  static constexpr int NS = 1;
+  static constexpr const char* NAME = "dj_adagrad_update";
+  static constexpr const char* BUFFERS = "param, grad and accum";
+  static constexpr const char* STATE[NS] = {"accum"};
+  float* state[NS];
+  float lr, eps, l2x2, grad_scale;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * grad_scale + l2x2 * p;
+    s[0] = s[0] + ge * ge;
+    p = p - (lr * ge) / (sqrtf(s[0]) + eps);
+  }
+};
+
+// Adam's first moment; u = max(b2*u, |g'|), the infinity norm, with np.maximum's NaN; no square root
+struct DjAdamaxRule {
+  static constexpr int NS = 2;
+  static constexpr const char* NAME = "dj_adamax_update";
+  static constexpr const char* BUFFERS = "param, grad, m and u";
+  static constexpr const char* STATE[NS] = {"m", "u"};
+  float* state[NS];
+  float lr_t, b1, b2, omb1, eps, l2x2, grad_scale;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * grad_scale + l2x2 * p;
+    s[0] = b1 * s[0] + omb1 * ge;
+    s[1] = max_nan(b2 * s[1], __builtin_fabsf(ge));
+    p = p - (lr_t * s[0]) / (s[1] + eps);
+  }
+};
+
+struct DjNadamScalars {
+  float lr, b1, b2, omb1, omb2, eps, c_g, c_m, c_v, omc_t, mc_t1, l2x2, grad_scale;
+};
+
+// Adam's two moments, each bias-corrected by a product with a reciprocal the caller made (c_g, c_m, c_v), and the
+// Nesterov mix mbar = (1 - mc_t)*g'*c_g + mc_t1*m*c_m of the momentum schedule
+struct DjNadamRule {
+  static constexpr int NS = 2;
+  static constexpr const char* NAME = "dj_nadam_update";
+  static constexpr const char* BUFFERS = "param, grad, m and v";
+  static constexpr const char* STATE[NS] = {"m", "v"};
+  float* state[NS];
+  DjNadamScalars k;
+  __device__ __forceinline__ void element(float& p, float g, float (&s)[NS]) const {
+    const float ge = g * k.grad_scale + k.l2x2 * p;
+    s[0] = k.b1 * s[0] + k.omb1 * ge;
+    s[1] = k.b2 * s[1] + k.omb2 * (ge * ge);
+    const float mbar = k.omc_t * (ge * k.c_g) + k.mc_t1 * (s[0] * k.c_m);
+    p = p - (k.lr * mbar) / (sqrtf(s[1] * k.c_v) + k.eps);
   }
 };
 
@@ -223,4 +292,29 @@ extern "C" int dj_adadelta_update(float* param, const float* grad, float* accum,
   return optim_launch(param, grad, n,
                       DjAdadeltaRule{{accum, delta_accum}, lr, rho, one_minus_rho, epsilon, 2.f * l2, grad_scale}, sumsq,
                       stream);
+}
+
+extern "C" int dj_rmsprop_update(float* param, const float* grad, float* accum, long n, float lr, float rho, float epsilon,
+                                 float l2, float grad_scale, float* sumsq, void* stream) {
+  return optim_launch(param, grad, n, DjRmspropRule{{accum}, lr, rho, 1.f - rho, epsilon, 2.f * l2, grad_scale}, sumsq,
+                      stream);
+}
+
+extern "C" int dj_adagrad_update(float* param, const float* grad, float* accum, long n, float lr, float epsilon, float l2,
+                                 float grad_scale, float* sumsq, void* stream) {
+  return optim_launch(param, grad, n, DjAdagradRule{{accum}, lr, epsilon, 2.f * l2, grad_scale}, sumsq, stream);
+}
+
+extern "C" int dj_adamax_update(float* param, const float* grad, float* m, float* u, long n, float lr_t, float beta_1,
+                                float beta_2, float epsilon, float l2, float grad_scale, float* sumsq, void* stream) {
+  return optim_launch(param, grad, n, DjAdamaxRule{{m, u}, lr_t, beta_1, beta_2, 1.f - beta_1, epsilon, 2.f * l2, grad_scale},
+                      sumsq, stream);
+}
+
+extern "C" int dj_nadam_update(float* param, const float* grad, float* m, float* v, long n, float lr, float beta_1,
+                               float beta_2, float epsilon, float c_g, float c_m, float c_v, float one_minus_mc_t,
+                               float mc_t1, float l2, float grad_scale, float* sumsq, void* stream) {
+  const DjNadamScalars k = {lr, beta_1, beta_2, 1.f - beta_1, 1.f - beta_2, epsilon, c_g, c_m,
+                            c_v, one_minus_mc_t, mc_t1, 2.f * l2, grad_scale};
+  return optim_launch(param, grad, n, DjNadamRule{{m, v}, k}, sumsq, stream);
 }

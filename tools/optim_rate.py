@@ -1,12 +1,12 @@
-"""Achieved bandwidth of the optimizer update kernels: dj_sgd_momentum_update, dj_adam_update (plain and amsgrad) and
-dj_adadelta_update, each as ONE launch over n elements, for n = the trainable parameters of the deconv SSD300 and of
+"""Achieved bandwidth of the optimizer update kernels: dj_sgd_momentum_update, dj_adam_update (plain and amsgrad),
+dj_adadelta_update, dj_rmsprop_update, dj_adagrad_update, dj_adamax_update and dj_nadam_update, each as ONE launch over n elements, for n = the trainable parameters of the deconv SSD300 and of
 vgga_dct (as laid out in the flat buffer).  Per launch: bytes moved (every stream read once and written once), microseconds
 (the median of 20 samples after warm-up; a sample is --reps launches back to back between two events) and GB/s.
 
     python tools/optim_rate.py                    # the table
     python tools/optim_rate.py --train-step       # also: one SSD300 training step (deconv, B=32) with SGD and with Adam
 
-The three are rules of one kernel (csrc/dj_optim.hip), so none is a yardstick for the others: a change of that kernel is
+All are rules of one kernel (csrc/dj_optim.hip), so none is a yardstick for the others: a change of that kernel is
 measured against the build before it, the two libraries alternating in one session (DJ_LIB_PATH selects the library)."""
 import argparse
 import os
@@ -20,7 +20,7 @@ import torch
 from jpeg_detection_resnet_ssd_amd import workloads
 from jpeg_detection_resnet_ssd_amd.engine import call
 from jpeg_detection_resnet_ssd_amd.keras import backend as K
-from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD, Adam
+from jpeg_detection_resnet_ssd_amd.keras.optimizers import SGD, Adam, Nadam
 
 SAMPLES, WARMUP = 20, 5
 
@@ -49,6 +49,11 @@ def launches(n, dev):
         "dj_adam_update amsgrad": (36, lambda: call("dj_adam_update", p, g, s1, s2, s3, n, 1e-3, 0.9, 0.999, 1e-7, 5e-4, 1.0,
                                                     ssq)),
         "dj_adadelta_update": (28, lambda: call("dj_adadelta_update", p, g, s1, s2, n, 1.0, 0.95, 0.05, 1e-7, 5e-4, 1.0, ssq)),
+        "dj_rmsprop_update": (20, lambda: call("dj_rmsprop_update", p, g, s1, n, 1e-3, 0.9, 1e-7, 5e-4, 1.0, ssq)),
+        "dj_adagrad_update": (20, lambda: call("dj_adagrad_update", p, g, s1, n, 1e-2, 1e-7, 5e-4, 1.0, ssq)),
+        "dj_adamax_update": (28, lambda: call("dj_adamax_update", p, g, s1, s2, n, 2e-2, 0.9, 0.999, 1e-7, 5e-4, 1.0, ssq)),
+        "dj_nadam_update": (28, lambda: call("dj_nadam_update", p, g, s1, s2, n, 2e-3, 0.9, 0.999, 1e-7, *Nadam().step_scalars(),
+                                             5e-4, 1.0, ssq)),
     }
 
 
